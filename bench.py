@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the STonKGs pre-training hot path on MI355X (BASELINE.json metric: text-triple pairs/sec, whole node).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -10,6 +10,11 @@ A "step" = one full training step of STonKGsForPreTraining on one synthetic batc
 backbone, bf16 MFMA compute / fp32 master weights): frozen backbone forward, KG gather, encoder forward, heads,
 3 x cross-entropy, full backward, gradient all-reduce (N > 1), global-norm clip, AdamW, weight refresh.
 Inputs are resident in HBM before the timed region. Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and reports. --dump-outputs DIR also writes what the last timed step
+computed (dump_outputs). --full adds the figures that take runs of their own: the instrumented roofline / all-GEMM /
+encoder-path steps (--no-roofline drops them, --roofline-alone adds one more pair) and the CPU oracle baseline
+(--no-cpu-baseline drops it).
 """
 from __future__ import annotations
 
@@ -104,13 +109,21 @@ def parse():
     ap.add_argument("--batch", type=int, default=None, help="per-GPU batch (default 64, BASELINE config 2)")
     ap.add_argument("--model", choices=sorted(MODELS), default="150k",
                     help="150k = BASELINE config 2/3 (12L/768h, the headline); 24L1024 = config 4 (synthetic scale-up)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32; see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the instrumented roofline steps and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) without the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="(--full) without the instrumented roofline steps")
     ap.add_argument("--roofline-alone", action="store_true",
-                    help="two more instrumented steps WITHOUT the second stream: the dominant kernel's own efficiency as a "
-                         "labelled extra field (off by default, so that a rocprofv3 summary of the default command holds "
-                         "in-step launches only and reproduces roofline.frac)")
+                    help="(--full) two more instrumented steps WITHOUT the second stream: the dominant kernel's own "
+                         "efficiency as a labelled extra field (off by default, so that a rocprofv3 summary of the "
+                         "--full command holds in-step launches only and reproduces roofline.frac)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.roofline_alone and not args.full:
+        ap.error("--roofline-alone needs --full")
     if args.batch is None:
         args.batch = MODELS[args.model]["batch"]
     return args
@@ -173,6 +186,41 @@ def cpu_baseline(cfg, seconds_budget=72.0):
         n8, dt8 = timed(8, seconds_budget * 0.2, 2, 1)
         out["at_8_threads"] = {"value": B * n8 / dt8, "cores": 8, "steps": n8}
     return out
+
+
+DUMP_PER_TENSOR = 4096   # --dump-outputs: elements kept per trainable tensor (under 2 MB in all at 12L/768)
+
+
+def dump_outputs(out_dir, model, loss):
+    """--dump-outputs DIR: what a caller of the timed path holds after its last step - the loss `training_step` returned
+    and the model it updated - as float32 arrays DIR/<name>.npy:
+      loss    [4]  the loss and its terms (text MLM, entity MLM, NSP)
+      params       the trainable fp32 master weights after the step's AdamW update: every trainable tensor in name order,
+                   all of it up to DUMP_PER_TENSOR elements, beyond that DUMP_PER_TENSOR elements drawn from a generator
+                   seeded with 0.
+    Optimizer state (Adam's moments, the clipped gradient norm) stays inside the trainer and is not written.
+    The weights, batches and dropout masks are seeded, so every run starts from the same inputs. The step is not bitwise
+    repeatable: its reductions (split-K weight gradients, the decoders' dgrad, LayerNorm and loss sums) use fp32 atomics,
+    whose order varies, and the training trajectory carries those last-bit differences forward from step to step."""
+    import numpy as np
+
+    torch.cuda.synchronize()
+    gen = torch.Generator().manual_seed(0)
+    params = []
+    for name, p in sorted(model.named_parameters(), key=lambda kv: kv[0]):
+        if not p.requires_grad:
+            continue
+        flat = p.detach().reshape(-1)
+        n = flat.numel()
+        idx = torch.arange(n) if n <= DUMP_PER_TENSOR else torch.randint(0, n, (DUMP_PER_TENSOR,), generator=gen)
+        params.append(flat[idx.to(flat.device)])
+    out = {"loss": torch.stack([loss.detach().reshape(())] + [t.reshape(()) for t in model.last_loss_terms]),
+           "params": torch.cat(params)}
+    os.makedirs(out_dir, exist_ok=True)
+    for key, t in out.items():
+        np.save(os.path.join(out_dir, key + ".npy"), t.float().cpu().numpy())
+    log(f"outputs of the last timed step written to {out_dir}: "
+        + ", ".join(f"{k} {tuple(t.shape)}" for k, t in out.items()))
 
 
 def spawn_ranks(args) -> int:
@@ -267,11 +315,13 @@ def main():
         dt = float(t.item())
     final_loss = float(loss)
     log(f"timed: {dt / args.steps * 1e3:.2f} ms/step, loss {final_loss:.4f}")
+    if args.dump_outputs and rank == 0:   # (before the instrumented steps of --full move the weights on)
+        dump_outputs(args.dump_outputs, model, loss)
 
     roofline = None
     gemm_all = None
     encoder_path = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # dominant kernel of the step (rocprofv3 kernel-trace of this same command, profiles/): the weight-gradient GEMM.
         # Every GEMM launch of two extra steps is bracketed by HIP events ON THE STREAM IT IS LAUNCHED ON, in the launch
         # configuration the timed steps use (weight gradients on the second stream with their CU share, beside the dgrad
@@ -366,11 +416,11 @@ def main():
                                          "encoder ran: positions that are neither live keys, nor labelled, nor position 0 "
                                          "are dropped - no loss term or gradient reads them; the last layer's feed-forward "
                                          "block, the pooler and the head transform run on the labelled rows + position 0"},
-               "step_mfma_frac": round(value * gfl / 1e3 / (PEAK_BF16_TFLOPS * world), 4),
-               "roofline": roofline, "all_gemm": gemm_all,
-               "encoder_path": encoder_path}
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(cfg)
+               "step_mfma_frac": round(value * gfl / 1e3 / (PEAK_BF16_TFLOPS * world), 4)}
+        if args.full:
+            out.update(roofline=roofline, all_gemm=gemm_all, encoder_path=encoder_path)
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(cfg)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

@@ -292,6 +292,7 @@ def test_bench_contract_constants():
     finally:
         sys.argv = old
     assert a.gpus == 1 and 0 < a.steps <= 50 and 0 < a.warmup <= 10 and a.batch == 64
+    assert not a.full and a.dump_outputs is None   # a plain run: set up, warm up, time, report
     assert bench.PEAK_BF16_TFLOPS == 2500.0
     line = json.load(open(os.path.join(ROOT, "profiles", "r02_final_bench.json")))
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",

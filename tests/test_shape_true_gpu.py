@@ -488,3 +488,29 @@ def test_bench_configuration_packed_step_equals_padded_step(hip):
     for k in s0:
         e = float((s1[k] - s0[k]).norm() / s0[k].norm())
         assert e < 2e-2, (k, e)
+
+
+def test_bench_plain_run_and_its_dumped_outputs(hip, tmp_path):
+    """`bench.py --gpus 1 --steps 2 --warmup 1 --dump-outputs DIR` as every change is measured: one JSON line with the
+    headline fields and none of what takes runs of its own (`--full`), and in DIR what the last timed step computed -
+    the loss it returned (the reported final loss) and a sample of the weights it updated: float32, finite, < 64 MB."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["unit"] == "pairs/s" and line["higher_is_better"] is True and line["dtype"] == "bf16"
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["ms_per_step"] > 0
+    assert abs(line["value"] - 64 * 1e3 / line["ms_per_step"]) < 1e-2 * line["value"]
+    assert not {"roofline", "all_gemm", "encoder_path", "cpu_baseline"} & set(line)
+    out = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert set(out) == {"loss", "params"}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in out.values())
+    assert sum(a.nbytes for a in out.values()) < 64 << 20
+    assert out["loss"].shape == (4,) and abs(float(out["loss"][0]) - line["final_loss"]) < 1e-3
+    assert out["params"].size > 100_000 and np.abs(out["params"]).max() > 0

@@ -53,8 +53,8 @@ Everything below was taken on the round's FINAL code (one `gpurun` call, one box
 
 | file | what | command |
 |---|---|---|
-| `r04_final_bench.json` | the bench line as the driver runs it (20 steps, 5 warm-up, CPU baseline on) | `python bench.py` |
-| `r04_kernel_stats.csv`, `r04_bench_under_rocprof.json` | rocprofv3 per-kernel summary of the bench (9 steps: 2 warm-up + 5 timed + 2 instrumented) and the line it printed | `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline` (`tools/final_profiles.sh`) |
+| `r04_final_bench.json` | the bench line as the driver runs it (20 steps, 5 warm-up, CPU baseline on) | `python bench.py --full` |
+| `r04_kernel_stats.csv`, `r04_bench_under_rocprof.json` | rocprofv3 per-kernel summary of the bench (9 steps: 2 warm-up + 5 timed + 2 instrumented) and the line it printed | `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline` (`tools/final_profiles.sh`) |
 | `r04_pmc_traffic.csv` | per-kernel bytes at the L2's memory side (two passes, condensed by `tools/summarize_pmc.py`) | `rocprofv3 --kernel-trace --pmc FETCH_SIZE -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-roofline`, then `--pmc WRITE_SIZE` (`tools/final_pmc.sh`) |
 | `r04_pmc_mfma.csv` | per-kernel SQ counters (matrix-pipe utilisation; share of wave time parked at waits / ready but not issued / issuing VALU / LDS; `tools/summarize_pmc_sq.py`) | third pass of `tools/final_pmc.sh` |
 | `r04_ab_libs.log` | the library of the round's first profile commit (3fa1a35) against the final one, the bench alternating between them in one call: what the second half of the round bought | `tools/build_ref_lib.sh 3fa1a35; bash tools/ab_libs.sh 3 40` |
@@ -70,7 +70,7 @@ Everything below was taken on the round's FINAL code (one `gpurun` call, one box
 | `r04_trace_gaps.txt` | union of all kernels' intervals over two steps: how long NO kernel runs, and the framework's own small launches | `bash tools/trace_gaps.sh` |
 | `r04_step_series.log`, `r04_bench_kw.log` | per-step GPU time of a 50-step run (settled from the second step on) and the bench repeated with different K / W on one box (run-to-run spread of one build on one box: 26.3 - 26.8 ms) | `python tools/step_series.py 50`, `bash tools/bench_kw.sh` |
 | `r04_parity_envelopes.log` | what the round's new parity tests print: HIP gradients against the reference's own bf16-autocast gradients (g16 / g17), the HIP loss curves against the reference's fp32 AND bf16 curves (g11 / g12) | `pytest tests/test_shape_true_gpu.py tests/test_losscurve_gpu.py -s -k "real_depth or config5_on_12 or envelope"` |
-| `r04_c4_24L1024_bench.json` | BASELINE config 4 (24L / 1024h / 16 heads / 4096, batch 64) | `python bench.py --model 24L1024 --steps 10 --warmup 3 --no-cpu-baseline` |
+| `r04_c4_24L1024_bench.json` | BASELINE config 4 (24L / 1024h / 16 heads / 4096, batch 64) | `python bench.py --full --model 24L1024 --steps 10 --warmup 3 --no-cpu-baseline` |
 
 ## Headline (round 4)
 
