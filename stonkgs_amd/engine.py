@@ -85,31 +85,13 @@ class Engine:
         # Set by the trainer when gradients are all-reduced while backward runs (world size > 1): RCCL's kernels then hold
         # some CUs for the length of a collective, and a PERSISTENT one-workgroup-per-CU kernel with a static tile split
         # would wait for them (its late workgroups own a share of the tiles). Backward's persistent launches on the main
-        # stream (the dgrad GEMMs of every layer, `_kernel(site, True)`) are then launched STONK_GEMM_DISPATCHED: the
-        # same four-wave kernel with one work item per workgroup, so the hardware dispatcher hands out the tiles (one GPU,
-        # nothing beside it: +0.9 ms per step against the persistent grids; the 128x128 kernel used here before: +1.7 ms).
+        # stream (the dgrad GEMMs of every layer, `_kernel(site, True)`) are then launched STONK_GEMM_DISPATCHED2: the
+        # same four-wave kernel with two work items per workgroup, so the hardware dispatcher hands out the tiles and
+        # every second tile boundary keeps its prefetch (what it costs with nothing beside it: DESIGN.md section 6).
         self.comm_overlap = False
-        # ... with TWO work items per workgroup (STONK_GEMM_DISPATCHED2, round 3): every second tile boundary keeps its
-        # prefetch; measured on one GPU with nothing beside it (tools/ab_step.py dispatched_pairs engine.comm_overlap=1)
-        self.dispatched_pairs = True
-        self.decoder_dgrad_256 = True
-        # LayerNorm backward: dgamma / dbeta partial sums added on the weight-gradient stream (stonk_layernorm_bwd_reduce) instead
-        # of behind the kernel on the main one. Measured: +0.16 ms (26.87 against 26.71, tools/ab_step.py ln_reduce_side) - the
-        # 26 launches of ~7 us it takes off the main chain cost less there than the event record / wait pairs that order them: off
-        self.ln_reduce_side = False
-        self._ln_done = {}
-        # weight gradients whose row count is a multiple of 128 only (the text decoder's 29 056 = 113.5 x 256) on the
-        # written-out 256x256 kernel as well (its last row tile is half empty, the buffers' range checks drop what it
-        # adds): correct, and no change to the step - 26.76 against 26.77 ms interleaved (tools/ab_step.py tn_ragged) - so off
-        self.tn_ragged = False
-        # the label-sparse decoders' dgrad on gemm_a4.hip (fp32 atomics over a K split): measured SLOWER than the eight-wave
-        # kernel at these shapes - rows 58 / 350 KB apart, 737 against 612 us (entity) and 349 against 148 (text),
-        # tools/decoder_probe.py - so off; the decoders' FORWARD (fp16 logits) does run there: 687 against 888, 128 / 168
-        self.decoder_dgrad_a4 = False
-        self.decoder_fwd_a4 = True     # (False: the eight-wave kernel, as before round 4)
         # Which of the library's three NT kernels runs a launch is the LIBRARY's choice (STONK_GEMM_AUTO: from shape and
         # epilogue, stonk_gemm_nt_bf16) - except where the engine knows what the library cannot: that an all-reduce is
-        # running beside backward (comm_overlap -> the dynamically scheduled 128x128 kernel for the persistent launches).
+        # running beside backward (comm_overlap -> the dispatcher-scheduled form for the persistent launches).
         # `kernel_for` lets a tool pin a site for an A/B (tools/ab_step.py): "qkv", "attn_out", "ffn_up", "ffn_down",
         # "dgrad_gelu", "dgrad_resid", "dgrad_attn_out", "dgrad_head" -> hip.GEMM_*.
         self.kernel_for: Dict[str, int] = {}
@@ -128,11 +110,6 @@ class Engine:
         # rows first, the attention kernels compute the first rows of every sequence as queries only (`q_offsets`; keys and
         # values: every row), and the output projection + LayerNorm run on the gathered read rows.
         self.prune_last_attn = True
-        # attention backward with the dQ and the dK / dV kernels on two streams, delta by a small kernel in front of them
-        # (stonk_attention_bwd_phases). Measured: 30.33 against 30.05 ms per step - both kernels are VALU-bound and fill the
-        # chip on their own, side by side they only share it. Off; kept as a switch for tools/ab_step.py.
-        self.attn_bwd_two_streams = False
-        self._astream: Optional[torch.cuda.Stream] = None
         # The frozen backbone's forward depends on the batch's token ids and on frozen weights only: given a hint of the NEXT
         # batch (`next_input_ids`, set by the trainer) it is queued on a stream of its own at the start of the current step and
         # runs beside the current step's encoder forward, where no weight-gradient stream competes for the CUs.
@@ -152,25 +129,16 @@ class Engine:
         # stream after the last parameter write - called before the first trainable weight is read and by every accessor.
         self._opt_stream: Optional[torch.cuda.Stream] = None
         self._params_ready: Optional[torch.cuda.Event] = None
-        self._wt_ready: Optional[torch.cuda.Event] = None   # W^T copies refreshed behind the parameters (refresh_wt_deferred)
         # tools/step_marks.py: a list to collect (name, host time, event on the current stream, was the optimizer's
         # "parameters final" event already complete) at a few points of the step; None (default) = nothing is recorded
         self.marks: Optional[list] = None
         self._wgrad_done: Dict[int, torch.cuda.Event] = {}   # layer parity -> side-stream event after its last wgrad
         self._wt_desc = None   # (device table, entries, tiles) of the batched W^T refresh
-        # development switches, read ONCE here: the 128x128 weight-gradient kernel everywhere / the CU share of the
-        # side-stream weight gradients
-        self.tn_v1 = bool(os.environ.get("STONK_TN_V1"))
-        self.tn_cus = int(os.environ.get("STONK_TN_CUS", "160"))
+        self.tn_cus = 160         # CU share of the side-stream weight gradients (tools/sweep_engine_int.py)
         # roctx ranges around the blocks of SURVEY section 2.3 (K1 backbone ... K16 optimizer), so that a
         # `rocprofv3 --marker-trace --kernel-trace` timeline reads by block. Off unless STONK_ROCTX=1 (read once, here).
         self.roctx = bool(os.environ.get("STONK_ROCTX"))
         self.tn_min_k = 16384     # contraction length (rows) from which the four-wave kernel takes a weight gradient
-        # CU share of a weight gradient of fewer than 16 256x256 tiles (the 768 x 768 ones: 9 tiles); 0 = tn_cus. 80 CUs'
-        # worth (8 K splits instead of 17: half the float atomics for the same K loops) measured 29.81 against 29.98 ms per
-        # step - inside the box-to-box noise, and each such launch then takes longer on fewer CUs (the dominant kernel's
-        # average launch 246 -> 260 us): left at 0, kept as a switch for tools/ab_step.py
-        self.tn_cus_small = 0
         self.tn_min_tiles = 36    # 128x128 tiles of an output from which the four-wave kernel takes the gradient: 36 = the
                                   # 768 x 768 ones too (35.67 against 35.79 ms per step with 100, tools/sweep_engine_int.py)
 
@@ -192,14 +160,35 @@ class Engine:
         if not enabled:
             yield
             return
-        if self._opt_stream is None:
-            self._opt_stream = torch.cuda.Stream(device=self.device)
-        self._opt_stream.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(self._opt_stream):
+        with self._fork("_opt_stream") as stream:
             yield
             ev = torch.cuda.Event()
-            ev.record(self._opt_stream)
+            ev.record(stream)
         self._params_ready = ev
+
+    @contextlib.contextmanager
+    def _fork(self, attr: str):
+        """Run the body on the side stream kept in `self.<attr>` (created on first use), ordered after everything enqueued
+        so far on the current stream. Yields the side stream."""
+        side = getattr(self, attr)
+        if side is None:
+            side = torch.cuda.Stream(device=self.device)
+            setattr(self, attr, side)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            yield side
+
+    @contextlib.contextmanager
+    def _timed(self, kind: str, M, N, K, m_dev=None, k_dev=None):
+        """(GemmTimer only) bracket the body's launch with two timing events on the current stream and record it."""
+        if self.gemm_timer is None:
+            yield
+            return
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        yield
+        e1.record()
+        self.gemm_timer.records.append((kind, e0, e1, M, N, K, m_dev, k_dev))
 
     @contextlib.contextmanager
     def block(self, name: str):
@@ -249,35 +238,11 @@ class Engine:
         return self.buf("ln.ws", (n,), F32)
 
     def ln_bwd(self, dy, x, mean, rstd, gamma, dx, dx_drop, dgamma, dbeta, rows, H, flags, p_in, seed_in, p_out, seed_out):
-        """stonk_layernorm_bwd on the current stream. With the weight gradients on their own stream (`overlap_wgrad`) the sum
-        of the per-workgroup dgamma / dbeta partials can go there too (`ln_reduce_side`; off - measured slower, see __init__):
-        nothing on the main chain reads the two vectors. The partials then need a workspace of their own until that launch
-        has run: a ring of four, each slot guarded by the event of the reduce that last read it."""
-        st = hip.stream_ptr()
-        args = (hip.ptr(dy), hip.ptr(x), hip.ptr(mean), hip.ptr(rstd), hip.ptr(gamma), hip.ptr(dx), hip.ptr(dx_drop),
-                hip.ptr(dgamma), hip.ptr(dbeta), rows, H)
-        if not (self.ln_reduce_side and self.overlap_wgrad) or dgamma is None or rows == 0:
-            ws = self.ln_ws()
-            hip.call("stonk_layernorm_bwd", *args, flags, p_in, seed_in, p_out, seed_out, ws.data_ptr(), ws.numel(), st)
-            return
-        n = int(hip.lib().stonk_layernorm_bwd_workspace_floats(1 << 30, self.cfg.hidden_size))
-        slot = self._ln_slot = (getattr(self, "_ln_slot", -1) + 1) % 4
-        ws = self.buf(f"ln.ws.ring{slot}", (n,), F32)
-        last = self._ln_done.get(slot)
-        if last is not None:
-            torch.cuda.current_stream().wait_event(last)   # (the reduce of four LayerNorms ago: done long since)
-        hip.call("stonk_layernorm_bwd", *args, flags | hip.LN_DEFER_REDUCE, p_in, seed_in, p_out, seed_out, ws.data_ptr(),
-                 ws.numel(), st)
-        if self._wstream is None:
-            self._wstream = torch.cuda.Stream(device=self.device)
-        ready = torch.cuda.Event()
-        ready.record()
-        self._wstream.wait_event(ready)
-        with torch.cuda.stream(self._wstream):
-            hip.call("stonk_layernorm_bwd_reduce", ws.data_ptr(), rows, H, hip.ptr(dgamma), hip.ptr(dbeta), hip.stream_ptr())
-            done = torch.cuda.Event()
-            done.record()
-        self._ln_done[slot] = done
+        """stonk_layernorm_bwd on the current stream, with the shared partial-sum workspace."""
+        ws = self.ln_ws()
+        hip.call("stonk_layernorm_bwd", hip.ptr(dy), hip.ptr(x), hip.ptr(mean), hip.ptr(rstd), hip.ptr(gamma), hip.ptr(dx),
+                 hip.ptr(dx_drop), hip.ptr(dgamma), hip.ptr(dbeta), rows, H, flags, p_in, seed_in, p_out, seed_out,
+                 ws.data_ptr(), ws.numel(), hip.stream_ptr())
 
     def check_errors(self) -> None:
         """Raise for any flag the kernels set (one tiny D2H copy; call where a sync is acceptable)."""
@@ -291,19 +256,11 @@ class Engine:
 
     def gemm(self, A, B, C, M, N, K, flags=0, bias=None, resid=None, aux=None, alpha=1.0, split_k=1, m_dev=None,
              k_dev=None, drop_p=0.0, seed=0, kernel=hip.GEMM_AUTO):
-        st = hip.stream_ptr()
-        timed = self.gemm_timer is not None
-        if timed:
-            e0 = torch.cuda.Event(enable_timing=True)
-            e1 = torch.cuda.Event(enable_timing=True)
-            e0.record()
-        hip.call("stonk_gemm_nt_bf16", A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0), C.data_ptr(), C.stride(0),
-                 M, N, K, flags, hip.ptr(bias), hip.ptr(resid), 0 if resid is None else resid.stride(0), hip.ptr(aux),
-                 0 if aux is None else aux.stride(0), alpha, split_k, hip.ptr(m_dev), hip.ptr(k_dev), drop_p,
-                 seed & 0xFFFFFFFF, kernel, st)
-        if timed:
-            e1.record()
-            self.gemm_timer.records.append(("nt", e0, e1, M, N, K, m_dev, k_dev))
+        with self._timed("nt", M, N, K, m_dev, k_dev):
+            hip.call("stonk_gemm_nt_bf16", A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0), C.data_ptr(), C.stride(0),
+                     M, N, K, flags, hip.ptr(bias), hip.ptr(resid), 0 if resid is None else resid.stride(0), hip.ptr(aux),
+                     0 if aux is None else aux.stride(0), alpha, split_k, hip.ptr(m_dev), hip.ptr(k_dev), drop_p,
+                     seed & 0xFFFFFFFF, kernel, hip.stream_ptr())
 
     def _split_k(self, M, N, K, side_stream=False) -> int:
         # 128x128 tiles, two workgroups co-resident per CU = 512 slots on 256 CUs: the sweep in tools/sweep_wgrad.py
@@ -315,10 +272,7 @@ class Engine:
         # stream) the kernel is held to 160 CUs' worth of workgroups (split_k = -160): another -1.5 ms
         # ... and so does the entity decoder's 175 104 x 768 gradient (2052 unsplit tiles, device-side token count, 5.7 GB
         # operand extent - the kernel re-bases its buffer resources per K tile): 863 us against 966 alone, -0.27 ms in the step
-        if (tiles >= self.tn_min_tiles and K >= self.tn_min_k and (M % 256 == 0 or self.tn_ragged) and N % 256 == 0
-                and not self.tn_v1):
-            if side_stream and self.tn_cus_small and tiles < 64:   # (tiles counts 128x128 ones: 64 = 16 of 256x256)
-                return -self.tn_cus_small
+        if tiles >= self.tn_min_tiles and K >= self.tn_min_k and M % 256 == 0 and N % 256 == 0:
             return -self.tn_cus if side_stream else 0
         return max(1, min(32, 480 // tiles, K // 64))
 
@@ -328,22 +282,25 @@ class Engine:
         current one; a GemmTimer brackets it with events on THAT stream, in the same launch configuration."""
         side = self.overlap_wgrad
         split = self._split_k(M_out, N_in, T, side)
-        timed = self.gemm_timer is not None
-        if side:
-            if self._wstream is None:
-                self._wstream = torch.cuda.Stream(device=self.device)
-            ready = torch.cuda.Event()
-            ready.record()                       # dy (and x) are complete on the main stream at this point
-            self._wstream.wait_event(ready)
-        with (torch.cuda.stream(self._wstream) if side else contextlib.nullcontext()):
-            if timed:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
+        # (the fork: dy and x are complete on the main stream at this point)
+        with (self._fork("_wstream") if side else contextlib.nullcontext()), \
+                self._timed("tn_a4" if split <= 0 else "tn", M_out, N_in, T, None, k_dev):
             hip.call("stonk_gemm_tn_bf16", dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), dW.data_ptr(),
                      dW.stride(0), hip.ptr(db), M_out, N_in, T, alpha, split, hip.ptr(k_dev), hip.stream_ptr())
-            if timed:
-                e1.record()
-                self.gemm_timer.records.append(("tn_a4" if split <= 0 else "tn", e0, e1, M_out, N_in, T, None, k_dev))
+
+    def _gather_rows(self, src, rd_rows, cnt, dst, cap) -> None:
+        """dst[i] = src[rd_rows[i]] for the first cnt[0] rows (a device-side count); rows from the count up to the next
+        multiple of 128, at most `cap`, are zero-filled."""
+        H = self.cfg.hidden_size
+        hip.call("stonk_gather_rows_bf16", src.data_ptr(), H, rd_rows.data_ptr(), cnt.data_ptr(), dst.data_ptr(), H, H, cap,
+                 hip.stream_ptr())
+
+    def _scatter_rows_into_zeros(self, src, rd_rows, cnt, dst, T) -> None:
+        """dst[:T] = 0, then dst[rd_rows[i]] = src[i] for the first cnt[0] rows."""
+        H = self.cfg.hidden_size
+        dst[:T].zero_()
+        hip.call("stonk_scatter_rows_bf16", src.data_ptr(), H, rd_rows.data_ptr(), cnt.data_ptr(), dst.data_ptr(), H, H,
+                 hip.stream_ptr())
 
     def transpose(self, x, rows, cols, name, colsum=None, rows_dev=None):
         rpad = (rows + 63) // 64 * 64
@@ -359,42 +316,20 @@ class Engine:
         if k is not None:
             return k
         if persistent_in_backward and self.comm_overlap:
-            return hip.GEMM_DISPATCHED2 if self.dispatched_pairs else hip.GEMM_DISPATCHED
+            return hip.GEMM_DISPATCHED2
         return hip.GEMM_AUTO
 
     def seed(self, layer: int, site: int) -> int:
         return (self.seed_base * 0x9E3779B1 + layer * 64 + site) & 0xFFFFFFFF
 
     # ------------------------------------------------------------------ derived weights
-    def refresh_derived(self, bf16_mirror: bool = True, transposes: bool = True) -> None:
-        """bf16 mirrors (if the optimizer has not just written them) and W^T copies for dgrad. `transposes=False`: the caller
-        refreshes the W^T copies itself, later (`refresh_wt_deferred`)."""
+    def refresh_derived(self, bf16_mirror: bool = True) -> None:
+        """bf16 mirrors (if the optimizer has not just written them) and W^T copies for dgrad."""
         st = hip.stream_ptr()
         if bf16_mirror:
             for s in (self.P, self.BB):
                 hip.call("stonk_cast_f32_to_bf16", s.data.data_ptr(), s.bf16.data_ptr(), s.numel, st)
-        if transposes:
-            self.wait_wt()   # (a deferred refresh still in flight writes the same copies)
-            self._refresh_wt(st)
-
-    def refresh_wt_deferred(self) -> None:
-        """The W^T copies BEHIND the "parameters final" event (round 4): only backward's dgrad launches read them, ten
-        milliseconds into the next step, so the 0.2-ms transpose of 0.49 GB runs on the optimizer stream beside the next
-        step's forward instead of between AdamW and it; `backward` waits for `_wt_ready`."""
-        stream = self._opt_stream if self._opt_stream is not None and self._params_ready is not None else None
-        if stream is None:
-            self._refresh_wt(hip.stream_ptr())
-            return
-        with torch.cuda.stream(stream):
-            self._refresh_wt(hip.stream_ptr())
-            ev = torch.cuda.Event()
-            ev.record(stream)
-        self._wt_ready = ev
-
-    def wait_wt(self) -> None:
-        ev = self._wt_ready
-        if ev is not None:
-            torch.cuda.current_stream().wait_event(ev)
+        self._refresh_wt(st)
 
     def _refresh_wt(self, st) -> None:
         if self._wt_desc is None or self._wt_desc[3] != self.P.bf16.data_ptr():   # (the table holds raw addresses)
@@ -462,9 +397,8 @@ class Engine:
         if qattn:
             Ta = rd["T"]
             a_in, res = self.buf(f"{tag}.ctxrd", (cap, H)), self.buf(f"{tag}.xrd", (cap, H))
-            for src, dst in ((ctx, a_in), (x, res)):   # (rows from the count up to the next multiple of 128 are zero-filled)
-                hip.call("stonk_gather_rows_bf16", src.data_ptr(), H, rd["rows"].data_ptr(), rd["cnt"].data_ptr(),
-                         dst.data_ptr(), H, H, cap, st)
+            self._gather_rows(ctx, rd["rows"], rd["cnt"], a_in, cap)
+            self._gather_rows(x, rd["rows"], rd["cnt"], res, cap)
         s1 = self.buf(f"{tag}.s1", (cap, H))
         fl = hip.EPI_BIAS | hip.EPI_RESID | (hip.EPI_DROPOUT if p_hid > 0 else 0)
         self.gemm(a_in, w(prefix + ".attention.output.dense.weight"), s1, Ta, H, H, flags=fl,
@@ -478,8 +412,7 @@ class Engine:
         hf, Tf = h1, Ta                            # input rows of the feed-forward block
         if rd is not None and not qattn:
             hf, Tf = self.buf(f"{tag}.h1rd", (cap, H)), rd["T"]
-            hip.call("stonk_gather_rows_bf16", h1.data_ptr(), H, rd["rows"].data_ptr(), rd["cnt"].data_ptr(), hf.data_ptr(),
-                     H, H, cap, st)            # (rows from the count up to the next multiple of 128 are zero-filled)
+            self._gather_rows(h1, rd["rows"], rd["cnt"], hf, cap)
         g = self.buf(f"{tag}.g", (cap, I))
         u = self.buf(f"{tag}.u", (cap, I)) if save is not None else None
         fl = hip.EPI_BIAS | hip.EPI_GELU | ((hip.EPI_SAVE_PREACT | hip.EPI_AUX_GRAD) if save is not None else 0)
@@ -545,9 +478,7 @@ class Engine:
             dh1rd = self.buf("b.dh1rd", (cap, H))
             self.gemm(du, wt[prefix + ".intermediate.dense.weight"], dh1rd, Tf, H, I, flags=hip.EPI_RESID, resid=ds2,
                       kernel=self._kernel("dgrad_resid", True))
-            dh1[:T].zero_()
-            hip.call("stonk_scatter_rows_bf16", dh1rd.data_ptr(), H, rd["rows"].data_ptr(), rd["cnt"].data_ptr(),
-                     dh1.data_ptr(), H, H, st)
+            self._scatter_rows_into_zeros(dh1rd, rd["rows"], rd["cnt"], dh1, T)
         # ---- LN1 backward
         ds1 = self.buf(f"b.ds1.{par}", (cap, H))
         da = self.buf(f"b.da.{par}", (cap, H)) if p_hid > 0 else None
@@ -568,10 +499,8 @@ class Engine:
             self.gemm(da, wt[prefix + ".attention.output.dense.weight"], dctxrd, Ta, H, H,
                       kernel=self._kernel("dgrad_attn_out", True))
             ds1 = self.buf("b.ds1full", (cap, H))
-            for src, dst in ((dctxrd, dctx), (ds1rd, ds1)):
-                dst[:T].zero_()
-                hip.call("stonk_scatter_rows_bf16", src.data_ptr(), H, rd["rows"].data_ptr(), rd["cnt"].data_ptr(),
-                         dst.data_ptr(), H, H, st)
+            self._scatter_rows_into_zeros(dctxrd, rd["rows"], rd["cnt"], dctx, T)
+            self._scatter_rows_into_zeros(ds1rd, rd["rows"], rd["cnt"], ds1, T)
         # ---- attention core
         qkv = sv["qkv"]
         dqkv = self.buf(f"b.dqkv.{par}", (cap, 3 * H))
@@ -587,21 +516,7 @@ class Engine:
                  hip.ptr(qoff), sv["ctx"].data_ptr(), H, dctx.data_ptr(), H, sv["lse"].data_ptr(), delta.data_ptr(),
                  dqkv.data_ptr(), dqkv.data_ptr() + 2 * H, 3 * H, dqkv.data_ptr() + 4 * H, B, NH, seq, 64,
                  1.0 / math.sqrt(64.0), p_att, self.seed(lidx, 1))
-        if not self.attn_bwd_two_streams:
-            hip.call("stonk_attention_bwd", *aargs, st)
-        else:
-            if self._astream is None:
-                self._astream = torch.cuda.Stream(device=self.device)
-            hip.call("stonk_attention_bwd_phases", hip.ATTN_BWD_DELTA, *aargs, st)
-            fork = torch.cuda.Event()
-            fork.record()
-            self._astream.wait_event(fork)
-            with torch.cuda.stream(self._astream):
-                hip.call("stonk_attention_bwd_phases", hip.ATTN_BWD_DKV, *aargs, hip.stream_ptr())
-                join = torch.cuda.Event()
-                join.record()
-            hip.call("stonk_attention_bwd_phases", hip.ATTN_BWD_DQ, *aargs, st)
-            torch.cuda.current_stream().wait_event(join)
+        hip.call("stonk_attention_bwd", *aargs, st)
         # ---- QKV projection
         self.wgrad(dqkv, sv["x"], g_(prefix + ".attention.self.qkv.weight"), g_(prefix + ".attention.self.qkv.bias"),
                    3 * H, H, T)
@@ -641,14 +556,9 @@ class Engine:
         cfg = self.cfg
         H, S, half = cfg.hidden_size, cfg.max_position_embeddings, cfg.half_length
         B = input_ids.shape[0]
-        if self._bb_stream is None:
-            self._bb_stream = torch.cuda.Stream(device=self.device)
-        ready = torch.cuda.Event()
-        ready.record()
-        self._bb_stream.wait_event(ready)
         self._pref_par ^= 1
-        out = self.buf(f"bb.pref{self._pref_par}", (B * half, H))
-        with torch.cuda.stream(self._bb_stream):
+        out = self.buf(f"bb.pref{self._pref_par}", (B * half, H))   # (allocated, if it has to be, on the current stream)
+        with self._fork("_bb_stream"):
             # dropout masks are a function of (step counter, layer, site, element): the prefetched forward draws the masks
             # of the step that will CONSUME it (the counter advances once per encode), so a run that prefetches and one
             # that does not - or a resumed one - see the same masks
@@ -802,8 +712,7 @@ class Engine:
             nb = self.buf(f"{e}.nb", (1,), I32)
             nb.fill_(B)
             first, ld_first = self.buf(f"{e}.first", ((B + 127) // 128 * 128, H)), H
-            hip.call("stonk_gather_rows_bf16", seq_out.data_ptr(), H, first_rows.data_ptr(), nb.data_ptr(), first.data_ptr(),
-                     H, H, first.shape[0], st)
+            self._gather_rows(seq_out, first_rows, nb, first, first.shape[0])
         hip.call("stonk_small_linear_fwd", first.data_ptr(), ld_first, f("bert.pooler.dense.weight").data_ptr(),
                  f("bert.pooler.dense.bias").data_ptr(), pooled.data_ptr(), B, H, H, hip.SMALL_TANH, st)
         if save is not None:   # (None: forward-only callers - embedding extraction, batched inference)
@@ -862,14 +771,12 @@ class Engine:
                 hip.call("stonk_label_compact", labels.data_ptr(), cap, half, S, off, rows.data_ptr(), tg.data_ptr(),
                          cnt.data_ptr(), hip.ptr(row_of_pos), st)
                 hs = self.buf(f"l.{nm}.hs", (cap, H))
-                hip.call("stonk_gather_rows_bf16", t.data_ptr(), H, rows.data_ptr(), cnt.data_ptr(), hs.data_ptr(), H, H,
-                         cap, st)
+                self._gather_rows(t, rows, cnt, hs, cap)
                 # logits of the labelled rows only, in fp16 (11 significant bits; the softmax arithmetic stays fp32): the
                 # decoder GEMM writes and the cross-entropy reads 2 bytes per logit instead of 4 - both are HBM-bound on them
                 f16 = self.f16_logits
                 logits = self.buf(f"l.{nm}.logits", (cap, npad), torch.float16 if f16 else F32)
-                self.gemm(hs, w(wname), logits, cap, npad, H, flags=hip.EPI_OUT_F16 if f16 else hip.EPI_OUT_F32, m_dev=cnt,
-                          kernel=hip.GEMM_AUTO if self.decoder_fwd_a4 else hip.GEMM_WAVE8)
+                self.gemm(hs, w(wname), logits, cap, npad, H, flags=hip.EPI_OUT_F16 if f16 else hip.EPI_OUT_F32, m_dev=cnt)
                 dl = self.buf(f"l.{nm}.dl", (cap, npad)) if need_backward else None
                 hip.call("stonk_softmax_xent_f16_fwd_bwd" if f16 else "stonk_softmax_xent_fwd_bwd", logits.data_ptr(), npad,
                          N, npad, tg.data_ptr(), cnt.data_ptr(), acc[hi:hi + 1].data_ptr(), hip.ptr(dl), npad, 1.0, cap,
@@ -894,8 +801,7 @@ class Engine:
                 rows.copy_((torch.arange(cap, device=self.device, dtype=I32) // half) * S + off +
                            torch.arange(cap, device=self.device, dtype=I32) % half)
                 hs = self.buf("d.hs", (cap, H))
-                hip.call("stonk_gather_rows_bf16", t.data_ptr(), H, rows.data_ptr(), full.data_ptr(), hs.data_ptr(), H, H,
-                         cap, st)
+                self._gather_rows(t, rows, full, hs, cap)
                 # fresh tensor: handed to the caller, must not alias the workspace
                 logits = torch.empty(cap, npad, dtype=F32, device=self.device)
                 self.gemm(hs, w(wname), logits, cap, npad, H, flags=hip.EPI_OUT_F32)
@@ -913,7 +819,6 @@ class Engine:
         if sv is None:
             raise RuntimeError("backward() without a training forward (labels are required)")
         self.saved = None
-        self.wait_wt()
         cfg = self.cfg
         H, S, half = cfg.hidden_size, cfg.max_position_embeddings, cfg.half_length
         B = sv["B"]
@@ -939,13 +844,8 @@ class Engine:
             # tiles with 16: 734 us against 951 for the entity decoder (tools/bench_decoder_dgrad.py)
             # (not beside a running all-reduce - the entity decoder's bucket is in flight when the text decoder's dgrad is
             # launched: a persistent launch would wait for the CUs RCCL holds, tools/hog_test.py)
-            # (the written-out four-wave kernel on 256x192 tiles with as many K shares as fill the CUs once - it counts the
-            # live tiles itself, split_k is an upper bound - is the slower one here: see __init__)
-            if self.decoder_dgrad_a4 and cap >= 1024 and H % 192 == 0 and (npad // 64) % 2 == 0 and not (self.comm_overlap and nm != "ent"):
-                self.gemm(h["dl"], wt[wname], dhs, cap, H, npad, flags=hip.EPI_OUT_F32_ATOMIC, split_k=64, m_dev=h["cnt"],
-                          alpha=gscale, kernel=hip.GEMM_ASM4_192)
-            elif (self.decoder_dgrad_256 and npad >= 16384 and cap >= 1024 and H % 256 == 0
-                    and not (self.comm_overlap and nm != "ent")):
+            # (the written-out four-wave kernel on 256x192 tiles is the slower one here: DESIGN.md section 4.3)
+            if npad >= 16384 and cap >= 1024 and H % 256 == 0 and not (self.comm_overlap and nm != "ent"):
                 self.gemm(h["dl"], wt[wname], dhs, cap, H, npad, flags=hip.EPI_OUT_F32_ATOMIC, split_k=8, m_dev=h["cnt"],
                           alpha=gscale, kernel=hip.GEMM_WAVE8)
             else:
@@ -988,10 +888,7 @@ class Engine:
             if self._wstream is None:
                 hook(name)
                 return
-            ready = torch.cuda.Event()
-            ready.record()                      # bias / LayerNorm gradients written by main-stream kernels
-            self._wstream.wait_event(ready)
-            with torch.cuda.stream(self._wstream):
+            with self._fork("_wstream"):        # (behind the bias / LayerNorm gradients written by main-stream kernels)
                 hook(name)
         return notify
 
@@ -1016,8 +913,7 @@ class Engine:
             nb = self.buf("e.nb", (1,), I32)
             nb.fill_(B)
             acc, ld_acc = self.buf("b.dfirst", ((B + 127) // 128 * 128, H)), H
-            hip.call("stonk_gather_rows_bf16", dseq.data_ptr(), H, first_rows.data_ptr(), nb.data_ptr(), acc.data_ptr(), H,
-                     H, acc.shape[0], st)
+            self._gather_rows(dseq, first_rows, nb, acc, acc.shape[0])
         hip.call("stonk_small_linear_bwd", dpooled.data_ptr(), sv["pooled"].data_ptr(), sv["first"].data_ptr(),
                  sv["ld_first"], f("bert.pooler.dense.weight").data_ptr(), g_("bert.pooler.dense.weight").data_ptr(),
                  g_("bert.pooler.dense.bias").data_ptr(), 0, acc.data_ptr(), ld_acc, B, H, H, hip.SMALL_TANH, st)
@@ -1103,7 +999,6 @@ class Engine:
         if sv is None:
             raise RuntimeError("backward_cls() without a training forward (labels are required)")
         self.saved = None
-        self.wait_wt()
         cfg = self.cfg
         H, S = cfg.hidden_size, cfg.max_position_embeddings
         B, C = sv["B"], sv["num_labels"]

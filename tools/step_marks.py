@@ -22,7 +22,10 @@ tr = Trainer(model, TrainingArguments(per_device_train_batch_size=64, max_steps=
 for kv in sys.argv[1:]:
     where, _, rest = kv.partition(".")
     name, _, value = rest.partition("=")
-    setattr(model.engine if where == "engine" else tr.args, name, int(value))
+    owner = model.engine if where == "engine" else tr.args
+    if not hasattr(owner, name):   # (a name that is gone would silently pin nothing)
+        sys.exit(f"step_marks.py: {type(owner).__name__} has no attribute '{name}'")
+    setattr(owner, name, int(value))
 dev = model.device
 batches = [{k: v.to(dev) for k, v in synthetic_batch(64, cfg.vocab_size, cfg.kg_vocab_size, 512, seed=1234 + i).items()}
            for i in range(4)]

@@ -16,6 +16,8 @@ attr, values = sys.argv[1], [int(v) for v in sys.argv[2:]]
 cfg = STonKGsConfig()
 model = STonKGsForPreTraining(cfg, seed=0)
 tr = Trainer(model, TrainingArguments(per_device_train_batch_size=64, max_steps=10000))
+if not hasattr(model.engine, attr):   # (a name that is gone would silently sweep nothing)
+    sys.exit(f"sweep_engine_int.py: Engine has no attribute '{attr}'")
 dev = model.device
 batches = [{k: v.to(dev) for k, v in synthetic_batch(64, cfg.vocab_size, cfg.kg_vocab_size, 512, seed=1234 + i).items()}
            for i in range(4)]
