@@ -35,17 +35,6 @@ constexpr int LDS_BYTES = LDS_STAGES + 8 * 4096;  // + a private 4 KiB epilogue 
 // slot order inside a stage = DMA / first-use order
 constexpr int SLOT_A0 = 0, SLOT_B0 = 1, SLOT_B1 = 2, SLOT_A1 = 3;
 
-__device__ __forceinline__ void wait_vm4() { asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); }
-__device__ __forceinline__ void wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ void wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ void barrier() { __builtin_amdgcn_s_barrier(); }
-
-struct Work {
-  int m0, n0;       // tile origin
-  long k_begin;     // element offset of the first K tile
-  int nk;           // K tiles in this work item
-};
-
 // EPI >= 0: the epilogue flags are a compile-time constant (no dead side-operand loads for the compiler to guard with
 // vmcnt(0) - such a wait inside the epilogue rounds also waits for the previous round's STORES and costs ~2 us per
 // round); EPI < 0: flags read from the arguments at run time (rare combinations).
@@ -431,7 +420,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const GemmArgs p) {
   issue(SLOT_B1, 0);
   issue(SLOT_A1, 0);
   advance_prefetch();
-  wait_vm4();   // A-first, B-first landed (this wave's part)
+  wait_vm<4>();   // A-first, B-first landed (this wave's part)
   barrier();
   if (wr == 1) barrier();   // second wave-row runs one barrier behind
 
@@ -449,7 +438,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const GemmArgs p) {
   auto wait_keep = [&](bool plus4) {   // at most S (+4) youngest operations may stay outstanding
     if (S == 16) { if (plus4) asm volatile("s_waitcnt vmcnt(20)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); }
     else if (S == 32) { if (plus4) asm volatile("s_waitcnt vmcnt(36)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(32)" ::: "memory"); }
-    else { if (plus4) wait_vm4(); else wait_vm0(); }
+    else { if (plus4) wait_vm<4>(); else wait_vm<0>(); }
   };
   int mode = 0;           // 0 steady state, 1 / 2 = first / second K tile after a tile boundary
   bool ahead = false;     // mode 1: the K tile after this one was issued at the boundary
@@ -461,7 +450,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const GemmArgs p) {
       read_a(buf, SLOT_A0);
       read_b(buf, SLOT_B0, fb0);
       if (do_issue) issue(SLOT_A0, nb);
-      if (mode == 0) { if (do_issue) wait_vm4(); else wait_vm0(); }            // retires B-second of this K tile
+      if (mode == 0) { if (do_issue) wait_vm<4>(); else wait_vm<0>(); }            // retires B-second of this K tile
       else if (mode == 2) wait_keep(do_issue);
       barrier();
       wait_lgkm0();
@@ -472,7 +461,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const GemmArgs p) {
       // ---------------- phase 1: quadrant (A0, B1)
       read_b(buf, SLOT_B1, fb1);
       if (do_issue) issue(SLOT_B0, nb);
-      if (mode == 0) { if (do_issue) wait_vm4(); else wait_vm0(); }            // retires A-second of this K tile
+      if (mode == 0) { if (do_issue) wait_vm<4>(); else wait_vm<0>(); }            // retires A-second of this K tile
       else if (mode == 2) wait_keep(do_issue);
       barrier();
       wait_lgkm0();
@@ -496,8 +485,8 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const GemmArgs p) {
                                            // skips the boundary's early re-staging, so this late read is safe
       if (do_issue) issue(SLOT_A1, nb);
       if (mode == 1) { if (ahead) wait_keep(true); }                             // retires A-first, B-first of the next K tile
-      else if (do_issue) wait_vm4();
-      else wait_vm0();
+      else if (do_issue) wait_vm<4>();
+      else wait_vm<0>();
       barrier();
       if (TN) wait_lgkm0();
       __builtin_amdgcn_sched_barrier(0);
@@ -527,7 +516,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const GemmArgs p) {
       advance_prefetch();
       asm volatile("s_waitcnt vmcnt(8)" ::: "memory");   // E2: everything older than those 8 DMA has landed
     } else {
-      wait_vm0();
+      wait_vm<0>();
     }
     prefetch_side(cw, 1, side_b);
     store_tile(cw);   // E3
@@ -548,55 +537,32 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const GemmArgs p) {
   if (wr == 0) barrier();   // balance the stagger barrier
 }
 
-}  // namespace
-
-namespace {
 template <int OUT_MODE, int EPI, bool TN = false>
 int launch256(const GemmArgs& a, int grid, hipStream_t st) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)gemm256_kernel<OUT_MODE, EPI, TN>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    attr_done = true;
-  }
-  hipLaunchKernelGGL((gemm256_kernel<OUT_MODE, EPI, TN>), dim3(grid), dim3(512), LDS_BYTES, st, a);
-  return stonk_launch_status();
+  return launch_with_lds<gemm256_kernel<OUT_MODE, EPI, TN>, LDS_BYTES>(a, grid, 512, st);
 }
-}  // namespace
 
-static int cu_count() {
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return -1;
-    n_cu = prop.multiProcessorCount;
-  }
-  return n_cu;
+// one persistent workgroup per CU
+int grid256(const GemmArgs& a, int n_cu) {
+  const long tiles = (long)((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN) * a.split_k;
+  return (int)(tiles < n_cu ? tiles : n_cu);
 }
+
+}  // namespace
 
 // weight-gradient form (see gemm_tn.hip for the contract): C fp32 [M,N] += alpha * A[K,M]^T . B[K,N], bias[M] += colsum
 int stonk_gemm256_tn_launch(const GemmArgs& a, hipStream_t st) {
   const int n_cu = cu_count();
   if (n_cu <= 0) return (int)hipGetLastError();
-  const long tiles = (long)((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN) * a.split_k;
-  const int grid = (int)(tiles < n_cu ? tiles : n_cu);
-  return launch256<2, 0, true>(a, grid, st);
+  return launch256<2, 0, true>(a, grid256(a, n_cu), st);
 }
 
 int stonk_gemm256_launch(const GemmArgs& a, int out_mode, hipStream_t st) {
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return (int)hipGetLastError();
-    n_cu = prop.multiProcessorCount;
-  }
-  const long tiles = (long)((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN) * a.split_k;
-  const int grid = (int)(tiles < n_cu ? tiles : n_cu);
-  constexpr int B = STONK_EPI_BIAS, G = STONK_EPI_GELU, SV = STONK_EPI_SAVE_PREACT, GB = STONK_EPI_GELU_BWD,
-                R = STONK_EPI_RESID, D = STONK_EPI_DROPOUT, AG = STONK_EPI_AUX_GRAD;
-  const int epi = a.flags & (B | G | SV | GB | R | D | AG);
+  using namespace epi_bits;
+  const int n_cu = cu_count();
+  if (n_cu <= 0) return (int)hipGetLastError();
+  const int grid = grid256(a, n_cu);
+  const int epi = a.flags & MASK;
   if (out_mode == 1) return epi == 0 ? launch256<1, 0>(a, grid, st) : launch256<1, -1>(a, grid, st);
   if (out_mode == 2) return launch256<2, 0>(a, grid, st);
   if (out_mode == 3) return launch256<3, 0>(a, grid, st);

@@ -432,53 +432,46 @@ __global__ __launch_bounds__(256, 1) void gemm_a4_kernel(const GemmArgs p) {
 
 template <int EPI, int BN_>
 int launch_a4(const GemmArgs& a, int grid, hipStream_t st) {
-  static bool attr_done = false;   // (one process per GPU: the attribute is per function and device)
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)gemm_a4_kernel<EPI, BN_>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    attr_done = true;
-  }
-  hipLaunchKernelGGL((gemm_a4_kernel<EPI, BN_>), dim3(grid), dim3(256), LDS_BYTES, st, a);
-  return stonk_launch_status();
+  return launch_with_lds<gemm_a4_kernel<EPI, BN_>, LDS_BYTES>(a, grid, 256, st);
 }
 
 }  // namespace
+
+// Is there an instance of the kernel for this epilogue (flags & epi_bits::MASK), output type and tile width (256 | 192)?
+// Says what the switch blocks of the launcher below list; stonk_gemm_nt_bf16 asks it before it routes a launch here. Every
+// 192-wide bf16 instance has a 256-wide twin, so for a width the launcher chooses itself the answer at 256 holds.
+bool stonk_gemm_a4_has_instance(int epi, int out, int tile_n) {
+  using namespace epi_bits;
+  if (out == STONK_EPI_OUT_F16) return epi == 0 && tile_n == 256;
+  // (the atomic form on 256 x 192 tiles only: its 256-wide instance does not fit the compiler's half of the register file)
+  if (out == STONK_EPI_OUT_F32_ATOMIC) return epi == 0 && tile_n == 192;
+  if (out != STONK_EPI_OUT_BF16) return false;
+  if (tile_n == 192) return epi_has_192(epi);
+  return epi == 0 || epi == B || epi == (B | G) || epi == (B | G | SV) || epi == GB || epi == (B | G | SV | AG) ||
+         epi == (GB | AG) || epi == R || epi == (B | R) || epi == (B | R | D);
+}
 
 // Launcher used by stonk_gemm_nt_bf16 (gemm_bf16.hip). Requires K % 128 == 0, ld % 64 == 0, 256 rows of every operand within
 // 2^30 bytes, 16-byte aligned side operands; bf16 output: alpha == 1 and split_k == 1; fp16 output: the same, no epilogue;
 // atomic fp32 output: no epilogue, alpha as given, split_k an upper bound (the kernel takes as many shares as fill the grid
 // once; a share is rounded up to an even number of K tiles).
 // tile_n: 0 = choose, 256, 192. items_per_wg as gemm_w4.hip.
-// Returns STONK_ESHAPE for an epilogue this kernel has no instance of (the caller then takes another kernel).
+// Returns STONK_ESHAPE where stonk_gemm_a4_has_instance says no (an explicit STONK_GEMM_ASM4 / _ASM4_192 is refused with it).
 int stonk_gemm_a4_launch(const GemmArgs& a, int tile_n, int items_per_wg, hipStream_t st) {
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return (int)hipGetLastError();
-    n_cu = prop.multiProcessorCount;
-  }
-  constexpr int B = STONK_EPI_BIAS, G = STONK_EPI_GELU, SV = STONK_EPI_SAVE_PREACT, GB = STONK_EPI_GELU_BWD,
-                R = STONK_EPI_RESID, D = STONK_EPI_DROPOUT, AG = STONK_EPI_AUX_GRAD;
-  const int epi = a.flags & (B | G | SV | GB | R | D | AG);
+  using namespace epi_bits;
+  const int n_cu = cu_count();
+  if (n_cu <= 0) return (int)hipGetLastError();
+  const int epi = a.flags & MASK;
   const int out = a.flags & STONK_EPI_OUT_MASK;
-  if (out != STONK_EPI_OUT_BF16 && (epi != 0 || out == STONK_EPI_OUT_F32)) return STONK_ESHAPE;
-  const long ntm = (a.M + BM - 1) / BM;
-  const bool has192 = a.N % 192 == 0 && out != STONK_EPI_OUT_F16 &&
-                      (epi == 0 || epi == B || epi == R || epi == (B | R) || epi == (B | R | D));
+  const bool has192 = a.N % 192 == 0 && stonk_gemm_a4_has_instance(epi, out, 192);
   if (tile_n == 192 && !has192) return STONK_ESHAPE;
   const int nk_all = a.K / BK;
   const int per = a.split_k > 1 ? ((nk_all + 2 * a.split_k - 1) / (2 * a.split_k)) * 2 : nk_all;
-  const long nsp = (nk_all + per - 1) / per;   // (as the kernel counts them)
-  if (tile_n == 0) {
-    const long t256 = ntm * ((a.N + 255) / 256) * nsp, t192 = ntm * (a.N / 192) * nsp;
-    const long c256 = ((t256 + n_cu - 1) / n_cu) * 256, c192 = ((t192 + n_cu - 1) / n_cu) * 192;
-    tile_n = (has192 && c192 < c256) ? 192 : 256;
-  }
-  const long tiles = (tile_n == 192 ? ntm * (a.N / 192) : ntm * ((a.N + 255) / 256)) * nsp;
-  const int grid = (int)(items_per_wg > 0 ? (tiles + items_per_wg - 1) / items_per_wg : (tiles < n_cu ? tiles : n_cu));
+  const long nsp = (nk_all + per - 1) / per;   // K shares per tile (as the kernel counts them)
+  const int grid = tile_grid_256(a, has192, nsp, items_per_wg, n_cu, tile_n);
+  if (!stonk_gemm_a4_has_instance(epi, out, tile_n)) return STONK_ESHAPE;
   if (out == STONK_EPI_OUT_F16) return launch_a4<STONK_EPI_OUT_F16, 256>(a, grid, st);
-  // (the atomic form on 256 x 192 tiles only: its 256-wide instance does not fit the compiler's half of the register file)
-  if (out == STONK_EPI_OUT_F32_ATOMIC) return tile_n == 192 ? launch_a4<STONK_EPI_OUT_F32_ATOMIC, 192>(a, grid, st) : STONK_ESHAPE;
+  if (out == STONK_EPI_OUT_F32_ATOMIC) return launch_a4<STONK_EPI_OUT_F32_ATOMIC, 192>(a, grid, st);
   if (tile_n == 192) {
     switch (epi) {
       case 0: return launch_a4<0, 192>(a, grid, st);

@@ -19,10 +19,11 @@
 
 using namespace stonk_gemm;
 
-// defined in gemm256.hip
+// the other three NT kernels' launchers (gemm256.hip, gemm_w4.hip, gemm_a4.hip)
 int stonk_gemm256_launch(const GemmArgs& a, int out_mode, hipStream_t st);
 int stonk_gemm_w4_launch(const GemmArgs& a, int out_mode, int tile_n, int items_per_wg, hipStream_t st);
 int stonk_gemm_a4_launch(const GemmArgs& a, int tile_n, int items_per_wg, hipStream_t st);
+bool stonk_gemm_a4_has_instance(int epi, int out, int tile_n);
 
 namespace {
 
@@ -285,15 +286,41 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(const GemmArgs p) {
 
 template <int OUT_MODE, bool GLDS, int EPI>
 int launch(const GemmArgs& a, int grid, hipStream_t st) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)gemm_nt_kernel<OUT_MODE, GLDS, EPI>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS);
-    attr_done = true;
-  }
-  hipLaunchKernelGGL((gemm_nt_kernel<OUT_MODE, GLDS, EPI>), dim3(grid), dim3(256), GEMM_LDS, st, a);
-  return stonk_launch_status();
+  return launch_with_lds<gemm_nt_kernel<OUT_MODE, GLDS, EPI>, GEMM_LDS>(a, grid, 256, st);
 }
+
+// the 128x128 kernel of this file: takes every launch that passed stonk_gemm_nt_bf16's validation
+int launch_tile128(const GemmArgs& a, int out_mode, hipStream_t st) {
+  using namespace epi_bits;
+  const long tiles = (long)((a.M + BM - 1) / BM) * (a.N / BN) * a.split_k;
+  // with a device-side row count the grid is capped and blocks walk the tiles that exist at run time
+  const long cap = a.m_dev ? 4096 : tiles;
+  const int grid = (int)(tiles < cap ? tiles : cap);
+  const int epi = a.flags & MASK;
+  if (out_mode == STONK_EPI_OUT_F32_ATOMIC) return launch<2, true, -1>(a, grid, st);
+  if (out_mode == STONK_EPI_OUT_F16) return launch<3, true, 0>(a, grid, st);
+  if (out_mode == STONK_EPI_OUT_F32) return epi == 0 ? launch<1, true, 0>(a, grid, st) : launch<1, true, -1>(a, grid, st);
+  switch (epi) {
+    case 0: return launch<0, true, 0>(a, grid, st);
+    case B: return launch<0, true, B>(a, grid, st);
+    case B | G | SV: return launch<0, true, B | G | SV>(a, grid, st);
+    case GB: return launch<0, true, GB>(a, grid, st);
+    case B | G | SV | AG: return launch<0, true, B | G | SV | AG>(a, grid, st);
+    case GB | AG: return launch<0, true, GB | AG>(a, grid, st);
+    case R: return launch<0, true, R>(a, grid, st);
+    case B | R: return launch<0, true, B | R>(a, grid, st);
+    case B | R | D: return launch<0, true, B | R | D>(a, grid, st);
+    default: return launch<0, true, -1>(a, grid, st);
+  }
+}
+
+// what stonk_gemm_nt_bf16 decides: which of the four kernels, on which tile width (the four-wave kernels: 256, 192, or
+// 0 = their launcher chooses) and with how many work items per workgroup (0 = one persistent workgroup per CU)
+enum Family { REFUSED, TILE128, WAVE8, WAVE4, ASM4 };
+struct Route {
+  Family family;
+  int tile_n, items_per_wg;
+};
 
 }  // namespace
 
@@ -302,6 +329,7 @@ extern "C" int stonk_gemm_nt_bf16(const void* A, int64_t lda, const void* B, int
                                   int64_t ldr, void* aux, int64_t ldaux, float alpha, int split_k,
                                   const int* m_dev, const int* k_dev, float drop_p, uint32_t seed, int kernel,
                                   void* stream) {
+  // ---------------------------------------------------------------- 1. arguments
   STONK_CHECK_ARG(A && B && C, STONK_EINVAL);
   STONK_CHECK_ARG(kernel >= STONK_GEMM_AUTO && kernel <= STONK_GEMM_ASM4_192, STONK_EINVAL);
   STONK_CHECK_ARG(M >= 0 && N > 0 && K > 0, STONK_ESHAPE);
@@ -310,8 +338,9 @@ extern "C" int stonk_gemm_nt_bf16(const void* A, int64_t lda, const void* B, int
   STONK_CHECK_ARG(lda % 8 == 0 && ldb % 8 == 0 && ldc % 4 == 0, STONK_EALIGN);
   STONK_CHECK_ARG(((uintptr_t)A % 16 == 0) && ((uintptr_t)B % 16 == 0) && ((uintptr_t)C % 16 == 0), STONK_EALIGN);
   const int out_mode = flags & STONK_EPI_OUT_MASK;
+  const int epi = flags & epi_bits::MASK;
   if (out_mode == STONK_EPI_OUT_F16)   // plain conversion of the product: no other epilogue, no split
-    STONK_CHECK_ARG((flags & 0x1FC) == 0 && split_k == 1, STONK_EINVAL);
+    STONK_CHECK_ARG(epi == 0 && split_k == 1, STONK_EINVAL);
   STONK_CHECK_ARG(split_k == 1 || out_mode == STONK_EPI_OUT_F32_ATOMIC, STONK_EINVAL);
   if (flags & STONK_EPI_BIAS) STONK_CHECK_ARG(bias && ((uintptr_t)bias % 16 == 0), STONK_EINVAL);
   if (flags & STONK_EPI_RESID) STONK_CHECK_ARG(resid && ldr % 4 == 0, STONK_EINVAL);
@@ -330,109 +359,78 @@ extern "C" int stonk_gemm_nt_bf16(const void* A, int64_t lda, const void* B, int
   a.drop_scale = 1.0f / (1.0f - drop_p);
   a.seed = stonk_seed_mix(seed);
 
-  hipStream_t st = (hipStream_t)stream;
-  // large launches go to the persistent 256x256 kernel (gemm256.hip); small ones keep the 128x128 tiles
-  // measured on MI355X (tools/bench_kernels.py): the 256x256 kernel wins for wide outputs (N >= 2304, where its
-  // halved operand traffic per flop outweighs one-workgroup-per-CU epilogues); N = 768 quantises badly (3 column tiles)
-  // ... and epilogues that READ a second [M,N] operand (residual, saved pre-activation) still favour two co-resident
-  // workgroups per CU hiding each other's load latency (tools/bench_epilogue.py)
+  // ---------------------------------------------------------------- 2. what each kernel can take
+  const bool bf16_out = out_mode == STONK_EPI_OUT_BF16, atomic_out = out_mode == STONK_EPI_OUT_F32_ATOMIC;
   const bool both_sides = (flags & STONK_EPI_GELU_BWD) && (flags & STONK_EPI_RESID);
-  // (bias + dropout + residual has no constant-flag instance on the 256x256 kernel: it would spill)
-  const bool bdr = (flags & STONK_EPI_DROPOUT) && (flags & STONK_EPI_RESID);
-  const bool big = M >= 1024 && N >= 1536 && out_mode != STONK_EPI_OUT_F32_ATOMIC && !both_sides && !bdr;
-  // its epilogue moves 16-byte row segments: strides of every side operand must keep them aligned
-  const bool v2_ok = ldc % 8 == 0 && (!(flags & STONK_EPI_BIAS) || alpha == 1.0f) &&  // bias rides in the accumulators
-                      (!(flags & STONK_EPI_RESID) || (ldr % 8 == 0 && (uintptr_t)resid % 16 == 0)) &&
-                     (!(flags & (STONK_EPI_SAVE_PREACT | STONK_EPI_GELU_BWD)) ||
-                      (ldaux % 8 == 0 && (uintptr_t)aux % 16 == 0));
-  // the four-wave kernel walks K tiles in pairs: an even number per work item
-  // ... and addresses its operands with 32-bit byte offsets from a per-K-tile base, chunk-swizzled by XOR (ld % 64)
-  const bool w4_ok = ldc % 8 == 0 && !both_sides && out_mode != STONK_EPI_OUT_F16 && (K / BK) % (2 * split_k) == 0 && !k_dev && lda % 64 == 0 &&
-                     ldb % 64 == 0 && (long)M * lda < (1L << 30) && (long)N * ldb < (1L << 30) && (long)M * ldc * (out_mode == 0 ? 2 : 4) < (1L << 31) &&
-                     (!(flags & STONK_EPI_RESID) || (ldr % 8 == 0 && (uintptr_t)resid % 16 == 0)) &&
-                     (!(flags & (STONK_EPI_SAVE_PREACT | STONK_EPI_GELU_BWD)) ||
-                      (ldaux % 8 == 0 && (uintptr_t)aux % 16 == 0));
-  // AUTO, as measured in the training step (interleaved A/B, tools/ab_step.py):
-  //  * launches whose epilogue reads a second [M,N] operand (residual, saved GELU') go to the four-wave kernel: its
-  //    128x128 wave tiles halve the LDS bytes per flop and its epilogue requests the side operand a round ahead
-  //    (FFN-down / attention-output forward 157 against 174 us, dgrad + residual 152 against 177, dgrad through GELU' 172
-  //    against 200; -1.4 ms per step together) - on 256x192 tiles where those quantise better (N = 768: two full rounds
-  //    of the CUs instead of one and a half; another 8-21 % per launch);
-  //  * the label-sparse decoders (fp16 / fp32 output) and wide launches that tile evenly by 256 stay on the eight-wave kernel;
-  //  * everything else (N = 768 without a side operand, split-K atomics, small M) keeps the 128x128 tiles.
-  const bool w4_side = (flags & (STONK_EPI_RESID | STONK_EPI_GELU_BWD)) != 0;
-  const bool dispatched = kernel == STONK_GEMM_DISPATCHED || kernel == STONK_GEMM_DISPATCHED2;
-  int k = dispatched ? STONK_GEMM_AUTO : kernel;
-  if (k == STONK_GEMM_AUTO)
-    k = (w4_ok && w4_side && M >= 1024 && out_mode == STONK_EPI_OUT_BF16) ? STONK_GEMM_WAVE4
-        // FFN-up (bias + GELU, with or without the saved GELU'): the four-wave kernel, 36.20 against 36.58 ms per step in
-        // round 2's interleaved A/B (its GELU epilogue is the longest of the step; fused QKV on it changes nothing: 36.47 / 36.50)
-        : (w4_ok && big && (flags & STONK_EPI_GELU) && out_mode == STONK_EPI_OUT_BF16) ? STONK_GEMM_WAVE4
-        // fused QKV (bias only, N = 2304 = 12 x 192: six full rounds of the CUs instead of four and a half): 35.24 against
-        // 35.70 ms per step on 256x192 tiles, where the same kernel on 256x256 tiles changed nothing
-        : (w4_ok && big && (flags & 0x1FC) == STONK_EPI_BIAS && N % 192 == 0 && out_mode == STONK_EPI_OUT_BF16)
-              ? STONK_GEMM_WAVE4
-        : (v2_ok && big)                                                     ? STONK_GEMM_WAVE8
-        // ... and the plain N = 768 launches (attention-output dgrad, the head transform's dgrad) since the four-wave kernel
-        // has 256x192 tiles: 42.6 against 52.3 us (tools/bench_w4_tiles.py)
-        : (w4_ok && M >= 1024 && N % 192 == 0 && out_mode == STONK_EPI_OUT_BF16 && (flags & 0x1FC) == 0) ? STONK_GEMM_WAVE4
-                                                                             : STONK_GEMM_TILE128;
-  // the written-out four-wave kernel (gemm_a4.hip): no device-side K, one side operand at most; bf16 output with the fused
-  // epilogues (no K split, alpha = 1), or the plain product as fp16, or as fp32 added atomically over a K split. Its
-  // buffers start at a tile's first row: 256 rows of an operand must fit 2^30 bytes, the whole operand need not (16 384
-  // x 175 104 logits)
-  const bool a4_plain = (flags & 0x1FC) == 0;
-  const bool a4_ok = ldc % 8 == 0 && !both_sides && !k_dev && (K / BK) % 2 == 0 && lda % 64 == 0 && ldb % 64 == 0 &&
-                     lda < (1L << 20) && ldb < (1L << 20) && ldc < (1L << 20) &&
-                     (out_mode == STONK_EPI_OUT_BF16 ? (w4_ok && split_k == 1 && alpha == 1.0f)
-                      : out_mode == STONK_EPI_OUT_F16 ? (a4_plain && alpha == 1.0f)
-                      : out_mode == STONK_EPI_OUT_F32_ATOMIC ? a4_plain : false);
-  if (k == STONK_GEMM_ASM4 || k == STONK_GEMM_ASM4_192) {
-    STONK_CHECK_ARG(a4_ok, STONK_ESHAPE);
-    return stonk_gemm_a4_launch(a, k == STONK_GEMM_ASM4 ? 256 : 192, 0, st);
-  }
-  // AUTO (and DISPATCHED): every bf16-output launch of at least a thousand rows whose epilogue the written-out kernel has an
-  // instance of goes there (round 4, tools/a4_probe.py at 26 432 rows, alone, us: QKV 89 against 106 on the compiled
-  // four-wave kernel, attention-output 41 / 49, FFN-up 166 -> see profiles/ / 186, FFN-down 107 / 124, dgrad through GELU'
-  // 152 / 157, dgrad + residual 105 / 119 and 82 / 92, plain 768 x 768 36 / 39); it picks its tile width itself
-  // (fp16 logits too: round 4, the entity decoder 830 -> see profiles/ us; the atomic form only where the caller names it)
-  if ((kernel == STONK_GEMM_AUTO || dispatched) && a4_ok && M >= 1024 && out_mode != STONK_EPI_OUT_F32_ATOMIC) {
-    const int rc = stonk_gemm_a4_launch(a, 0, !dispatched ? 0 : (kernel == STONK_GEMM_DISPATCHED2 ? 2 : 1), st);
-    if (rc != STONK_ESHAPE) return rc;   // (an epilogue it has no instance of: the older kernels below)
-  }
-  if (k == STONK_GEMM_WAVE4 || k == STONK_GEMM_WAVE4_192) {
-    STONK_CHECK_ARG(w4_ok, STONK_ESHAPE);
-    // chosen by AUTO: the launcher also picks the tile width (256x192 where N = 768 / 2304 quantise better on 256 CUs)
-    const bool chosen = kernel == STONK_GEMM_AUTO || dispatched;
-    return stonk_gemm_w4_launch(a, out_mode, chosen ? 0 : (k == STONK_GEMM_WAVE4 ? 256 : 192),
-                                !dispatched ? 0 : (kernel == STONK_GEMM_DISPATCHED2 ? 2 : 1), st);
-  }
-  if (k == STONK_GEMM_WAVE8 && dispatched) k = STONK_GEMM_TILE128;
-  if (k == STONK_GEMM_WAVE8) {
-    STONK_CHECK_ARG(v2_ok, STONK_ESHAPE);
-    return stonk_gemm256_launch(a, out_mode, st);
-  }
-  const long tiles = (long)((M + BM - 1) / BM) * (N / BN) * split_k;
-  // with a device-side row count the grid is capped and blocks walk the tiles that exist at run time
-  const long cap = m_dev ? 4096 : tiles;
-  const int grid = (int)(tiles < cap ? tiles : cap);
-  constexpr int Bi = STONK_EPI_BIAS, G = STONK_EPI_GELU, SV = STONK_EPI_SAVE_PREACT, GB = STONK_EPI_GELU_BWD,
-                R = STONK_EPI_RESID, D = STONK_EPI_DROPOUT, AG = STONK_EPI_AUX_GRAD;
-  const int epi = flags & (Bi | G | SV | GB | R | D | AG);
-  if (out_mode == STONK_EPI_OUT_F32_ATOMIC) return launch<2, true, -1>(a, grid, st);
-  if (out_mode == STONK_EPI_OUT_F16) return launch<3, true, 0>(a, grid, st);
-  if (out_mode == STONK_EPI_OUT_F32) return epi == 0 ? launch<1, true, 0>(a, grid, st) : launch<1, true, -1>(a, grid, st);
-  switch (epi) {
-    case 0: return launch<0, true, 0>(a, grid, st);
-    case Bi: return launch<0, true, Bi>(a, grid, st);
-    case Bi | G | SV: return launch<0, true, Bi | G | SV>(a, grid, st);
-    case GB: return launch<0, true, GB>(a, grid, st);
-    case Bi | G | SV | AG: return launch<0, true, Bi | G | SV | AG>(a, grid, st);
-    case GB | AG: return launch<0, true, GB | AG>(a, grid, st);
-    case R: return launch<0, true, R>(a, grid, st);
-    case Bi | R: return launch<0, true, Bi | R>(a, grid, st);
-    case Bi | R | D: return launch<0, true, Bi | R | D>(a, grid, st);
-    default: return launch<0, true, -1>(a, grid, st);
+  // the kernels that move 16-byte row segments of the output and of the side operands: their strides must keep them aligned
+  const bool rows16 = ldc % 8 == 0 && (!(flags & STONK_EPI_RESID) || (ldr % 8 == 0 && (uintptr_t)resid % 16 == 0)) &&
+                      (!(flags & (STONK_EPI_SAVE_PREACT | STONK_EPI_GELU_BWD)) || (ldaux % 8 == 0 && (uintptr_t)aux % 16 == 0));
+  // eight-wave kernel (gemm256.hip): the bias rides in the accumulators
+  const bool wave8_ok = rows16 && (!(flags & STONK_EPI_BIAS) || alpha == 1.0f);
+  // four-wave kernel (gemm_w4.hip): one side operand at most, no fp16 output; it walks K tiles in pairs (an even number per
+  // work item, none of them behind a device-side K) and addresses its operands with 32-bit byte offsets from a per-K-tile
+  // base, chunk-swizzled by XOR (ld % 64)
+  const bool wave4_ok = rows16 && !both_sides && out_mode != STONK_EPI_OUT_F16 && (K / BK) % (2 * split_k) == 0 && !k_dev &&
+                        lda % 64 == 0 && ldb % 64 == 0 && (long)M * lda < (1L << 30) && (long)N * ldb < (1L << 30) &&
+                        (long)M * ldc * (bf16_out ? 2 : 4) < (1L << 31);
+  // written-out four-wave kernel (gemm_a4.hip): no device-side K, one side operand at most; bf16 output with the fused
+  // epilogues (no K split, alpha = 1, within the four-wave kernel's extents), or the plain product as fp16, or as fp32 added
+  // atomically over a K split. Its buffers start at a tile's first row: 256 rows of an operand must fit 2^30 bytes, the
+  // whole operand need not (16 384 x 175 104 logits)
+  const bool asm4_ok = ldc % 8 == 0 && !both_sides && !k_dev && (K / BK) % 2 == 0 && lda % 64 == 0 && ldb % 64 == 0 &&
+                       lda < (1L << 20) && ldb < (1L << 20) && ldc < (1L << 20) &&
+                       (bf16_out ? (wave4_ok && split_k == 1 && alpha == 1.0f)
+                        : out_mode == STONK_EPI_OUT_F16 ? (epi == 0 && alpha == 1.0f)
+                        : atomic_out ? epi == 0 : false);
+
+  // ---------------------------------------------------------------- 3. the kernel, its tile width, its items per workgroup
+  const Route route = [&]() -> Route {
+    switch (kernel) {   // an explicit kernel: taken, or refused if it cannot take the arguments
+      case STONK_GEMM_TILE128: return {TILE128, 0, 0};
+      case STONK_GEMM_WAVE8: return {wave8_ok ? WAVE8 : REFUSED, 0, 0};
+      case STONK_GEMM_WAVE4: return {wave4_ok ? WAVE4 : REFUSED, 256, 0};
+      case STONK_GEMM_WAVE4_192: return {wave4_ok ? WAVE4 : REFUSED, 192, 0};
+      case STONK_GEMM_ASM4: return {asm4_ok ? ASM4 : REFUSED, 256, 0};
+      case STONK_GEMM_ASM4_192: return {asm4_ok ? ASM4 : REFUSED, 192, 0};
+    }
+    // AUTO, and AUTO's choice handed out by the hardware dispatcher (DISPATCHED: one work item per workgroup, DISPATCHED2:
+    // two). The four-wave kernels choose their tile width themselves (256x192 where N = 768 / 2304 quantise better).
+    const int items = kernel == STONK_GEMM_DISPATCHED ? 1 : kernel == STONK_GEMM_DISPATCHED2 ? 2 : 0;
+    // Every launch of at least a thousand rows that the written-out kernel has an instance for goes there: bf16 with the
+    // step's epilogues, the fp16 logits; the atomic form only where the caller names it.
+    if (asm4_ok && M >= 1024 && !atomic_out && stonk_gemm_a4_has_instance(epi, out_mode, 256)) return {ASM4, 0, items};
+    // What is left - alpha != 1, an epilogue the written-out kernel has no instance of, an fp32 output, fewer rows - is
+    // shared out among the compiled kernels as measured in the training step before that kernel existed (DESIGN section
+    // 4.2; no arm is shadowed: the written-out kernel wants alpha == 1, these do not):
+    //  * bf16 launches whose epilogue reads a second [M,N] operand (residual, saved GELU'), FFN-up (bias + GELU), and a bias
+    //    alone where N tiles by 192 (fused QKV): the four-wave kernel - 128x128 wave tiles halve the LDS bytes per flop, and
+    //    its epilogue requests the side operand a round ahead;
+    const bool big = M >= 1024 && N >= 1536 && !atomic_out && !both_sides &&
+                     // (bias + dropout + residual has no constant-flag instance on the eight-wave kernel: it would spill)
+                     !((flags & STONK_EPI_DROPOUT) && (flags & STONK_EPI_RESID));
+    const bool side = (flags & (STONK_EPI_RESID | STONK_EPI_GELU_BWD)) != 0;
+    const bool wave4_rows = wave4_ok && M >= 1024 && bf16_out;
+    if (wave4_rows && (side || (big && ((flags & STONK_EPI_GELU) || (epi == STONK_EPI_BIAS && N % 192 == 0)))))
+      return {WAVE4, 0, items};
+    //  * other wide outputs (N >= 1536: the label-sparse decoders' fp32 output among them) halve their operand traffic per
+    //    flop on the eight-wave kernel's 256x256 tiles; it has no dispatched form: 128x128 tiles stand in for it;
+    if (wave8_ok && big) return {items ? TILE128 : WAVE8, 0, 0};
+    //  * the plain N = 768 launches (attention-output dgrad, the head transform's dgrad): four-wave, on 256x192 tiles;
+    if (wave4_rows && N % 192 == 0 && epi == 0) return {WAVE4, 0, items};
+    //  * everything else (N = 768 with three column tiles of 256, split-K atomics, small M) keeps the 128x128 tiles, two
+    //    co-resident workgroups per CU hiding each other's load latency.
+    return {TILE128, 0, 0};
+  }();
+
+  // ---------------------------------------------------------------- 4. launch
+  hipStream_t st = (hipStream_t)stream;
+  switch (route.family) {
+    // (an explicit tile width may still be refused by the four-wave launchers: no such instance, N % 192 != 0)
+    case ASM4: return stonk_gemm_a4_launch(a, route.tile_n, route.items_per_wg, st);
+    case WAVE4: return stonk_gemm_w4_launch(a, out_mode, route.tile_n, route.items_per_wg, st);
+    case WAVE8: return stonk_gemm256_launch(a, out_mode, st);
+    case TILE128: return launch_tile128(a, out_mode, st);
+    default: return STONK_ESHAPE;
   }
 }
 

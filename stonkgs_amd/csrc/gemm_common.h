@@ -1,5 +1,6 @@
-// Argument block and helpers shared by the two bf16 GEMM kernels (gemm_bf16.hip: 128x128 tiles, gemm256.hip:
-// persistent 256x256 tiles). See stonk_gemm_nt_bf16 in include/stonk_hip.h for the meaning of each field.
+// Argument block and helpers shared by the bf16 GEMM kernels (gemm_bf16.hip, gemm256.hip, gemm_w4.hip, gemm_a4.hip and the
+// weight-gradient forms gemm_tn.hip, gemm_tn_a4.hip): device-side epilogues, waits and tile mapping first, the launchers'
+// host-side helpers at the end. See stonk_gemm_nt_bf16 in include/stonk_hip.h for the meaning of each field.
 #pragma once
 #include "common.h"
 #include "stonk_flags.h"
@@ -33,6 +34,22 @@ __device__ __forceinline__ int xcd_remap(int b, int n) {
   return base + (b >> 3);
 }
 
+// raw s_barrier and counted waits (never __syncthreads, which would drain the loads in flight)
+__device__ __forceinline__ void barrier() { __builtin_amdgcn_s_barrier(); }
+template <int N>
+__device__ __forceinline__ void wait_vm() {
+  static_assert(N >= 0 && N <= 63, "vmcnt is six bits");
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+__device__ __forceinline__ void wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+
+// one work item of the persistent 256-row kernels whose K position is an element offset (gemm256.hip, gemm_w4.hip,
+// gemm_tn_a4.hip; gemm_a4.hip counts K tiles and keeps its own)
+struct Work {
+  int m0, n0;       // tile origin
+  long k_begin;     // element offset of the first K tile (TN: first token)
+  int nk;           // K tiles in this work item
+};
 
 // Fused epilogue on 4 consecutive output columns n..n+3 of row m (values already scaled by alpha).
 __device__ __forceinline__ f32x4 epilogue4(f32x4 v, const GemmArgs& p, int flags, int m, int n) {
@@ -158,6 +175,59 @@ __device__ __forceinline__ void epilogue8_pre(float (&v)[8], const GemmArgs& p, 
 #pragma unroll
     for (int r = 0; r < 8; ++r) v[r] += (float)s.res[r];
   }
+}
+
+// ---------------------------------------------------------------- host side: what every launcher does
+// Epilogue bits by their short names, for the launchers' switch (epi) blocks that name the compiled instances.
+namespace epi_bits {
+constexpr int B = STONK_EPI_BIAS, G = STONK_EPI_GELU, SV = STONK_EPI_SAVE_PREACT, GB = STONK_EPI_GELU_BWD,
+              R = STONK_EPI_RESID, D = STONK_EPI_DROPOUT, AG = STONK_EPI_AUX_GRAD;
+constexpr int MASK = B | G | SV | GB | R | D | AG;   // = 0x1FC: flags & MASK == 0 is the plain product
+}  // namespace epi_bits
+
+// CUs of the current device, asked once per process (one process per GPU); <= 0: the query failed, hipGetLastError() says why
+inline int cu_count() {
+  static int n_cu = 0;
+  if (n_cu == 0) {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return -1;
+    n_cu = prop.multiProcessorCount;
+  }
+  return n_cu;
+}
+
+// Launch of a kernel whose dynamic LDS exceeds the default limit: the attribute is per function (and device), so the
+// "already set" flag is per KERNEL - every instance of a kernel template has its own.
+template <auto KERNEL, int LDS, typename Args>
+int launch_with_lds(const Args& a, int grid, int block, hipStream_t st) {
+  static bool attr_done = false;
+  if (!attr_done) {
+    (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+    attr_done = true;
+  }
+  hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(block), LDS, st, a);
+  return stonk_launch_status();
+}
+
+// The four-wave kernels' 256 x (256 | 192) tiles (gemm_w4.hip, gemm_a4.hip). 192-wide instances exist for the epilogues of
+// the N = 768 launches (none, bias, residual, bias + residual [+ dropout]) ...
+inline bool epi_has_192(int e) {
+  using namespace epi_bits;
+  return e == 0 || e == B || e == R || e == (B | R) || e == (B | R | D);
+}
+// ... and are chosen (tile_n == 0 on entry) where they quantise better: time ~ rounds of the CUs x tile width (N = 768 at
+// 32 768 rows: two full rounds instead of one and a half; at 16 384 rows one full round instead of 3/4). Returns the grid:
+// one persistent workgroup per CU, or (items_per_wg > 0) work items / items_per_wg. k_shares: work items per output tile.
+inline int tile_grid_256(const GemmArgs& a, bool has192, long k_shares, int items_per_wg, int n_cu, int& tile_n) {
+  const long ntm = (a.M + 255) / 256;
+  const long t256 = ntm * ((a.N + 255) / 256) * k_shares, t192 = ntm * (a.N / 192) * k_shares;
+  if (tile_n == 0) {
+    const long c256 = ((t256 + n_cu - 1) / n_cu) * 256, c192 = ((t192 + n_cu - 1) / n_cu) * 192;
+    tile_n = (has192 && c192 < c256) ? 192 : 256;
+  }
+  const long tiles = tile_n == 192 ? t192 : t256;
+  return (int)(items_per_wg > 0 ? (tiles + items_per_wg - 1) / items_per_wg : (tiles < n_cu ? tiles : n_cu));
 }
 
 }  // namespace stonk_gemm

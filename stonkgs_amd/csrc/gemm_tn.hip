@@ -21,7 +21,6 @@
 
 // persistent 256x256 variant (gemm256.hip, TN = true)
 int stonk_gemm256_tn_launch(const stonk_gemm::GemmArgs& a, hipStream_t st);
-int stonk_gemm_tn_w4_launch(const stonk_gemm::GemmArgs& a, hipStream_t st);
 int stonk_gemm_tn_a4_launch(const stonk_gemm::GemmArgs& a, hipStream_t st);
 
 namespace {
@@ -30,6 +29,8 @@ constexpr int BM = 128, BN = 128, BK = 64;
 constexpr int TILE_BYTES = BK * 256;          // 16 KiB: 64 token rows x 128 features
 constexpr int STAGE_BYTES = 2 * TILE_BYTES;
 constexpr int TN_LDS = 2 * STAGE_BYTES;       // 64 KiB
+
+using stonk_gemm::xcd_remap;
 
 struct TnArgs {
   const bf16* A;   // dY [T, M']
@@ -42,12 +43,6 @@ struct TnArgs {
   float alpha;
   int split_k;
 };
-
-__device__ __forceinline__ int xcd_remap(int b, int n) {
-  const int q = n >> 3, r = n & 7, x = b & 7;
-  const int base = (x < r) ? x * (q + 1) : r * (q + 1) + (x - r) * q;
-  return base + (b >> 3);
-}
 
 __device__ __forceinline__ int row_swz(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
 
@@ -193,19 +188,15 @@ extern "C" int stonk_gemm_tn_bf16(const void* dY, int64_t lda, const void* X, in
   STONK_CHECK_ARG(M > 0 && N > 0 && K > 0 && M % BM == 0 && N % BN == 0, STONK_ESHAPE);
   STONK_CHECK_ARG(lda % 8 == 0 && ldb % 8 == 0, STONK_EALIGN);
   STONK_CHECK_ARG((uintptr_t)dY % 16 == 0 && (uintptr_t)X % 16 == 0, STONK_EALIGN);
-  // split_k == 0 selects the four-wave 256x256 kernel (gemm_tn_w4.hip) with an automatic split: work items = tiles x
-  // splits aimed at one full round of the CUs. split_k <= -16: the same kernel limited to -split_k CUs' worth of
-  // workgroups - for launches that run on a second stream beside other work: a persistent one-workgroup-per-CU kernel that
-  // takes every CU stalls the other stream until its workgroups retire (the step is 1.5 ms faster with the weight
-  // gradients on 160 of the 256 CUs). split_k == -1 keeps the older eight-wave 256x256 TN form of gemm256.hip.
+  // split_k <= 0: the 256x256 kernels with an automatic split, work items = tiles x splits aimed at one full round of the
+  // CUs. 0 (and -2 .. -15): the written-out four-wave kernel (gemm_tn_a4.hip) on all CUs. -16 .. -1024: the same kernel
+  // limited to -split_k CUs' worth of workgroups - for launches that run on a second stream beside other work: a persistent
+  // one-workgroup-per-CU kernel that takes every CU stalls the other stream until its workgroups retire (the step is 1.5 ms
+  // faster with the weight gradients on 160 of the 256 CUs). -1: the older eight-wave 256x256 TN form of gemm256.hip.
   if (split_k <= 0) {
     STONK_CHECK_ARG(M >= 256 && N >= 256, STONK_ESHAPE);
     // (operands are addressed per 64-token K tile: 64 rows of either operand must stay inside 32-bit byte offsets)
     STONK_CHECK_ARG(lda % 64 == 0 && ldb % 64 == 0 && lda < (1L << 23) && ldb < (1L << 23), STONK_ESHAPE);
-    // (split_k == -2, or <= -2016 = held to -split_k - 2000 CUs: the compiled four-wave kernel, gemm_tn_w4.hip, which the
-    // written-out one replaced in round 4 - kept reachable for A/B runs)
-    const bool old_w4 = split_k == -2 || split_k <= -2016;
-    if (old_w4) split_k = split_k == -2 ? 0 : split_k + 2000;
     STONK_CHECK_ARG(split_k >= -1024, STONK_ESHAPE);
     stonk_gemm::GemmArgs g = {};
     g.A = (const bf16*)dY; g.B = (const bf16*)X; g.C = dW; g.bias = dbias; g.k_dev = k_dev;
@@ -217,21 +208,13 @@ extern "C" int stonk_gemm_tn_bf16(const void* dY, int64_t lda, const void* X, in
     if (sk > nk / 8) sk = nk / 8 > 0 ? nk / 8 : 1;
     g.split_k = (int)sk;
     g.flags = (int)cus;   // grid cap
-    if (split_k != -1 && !old_w4) return stonk_gemm_tn_a4_launch(g, (hipStream_t)stream);
-    if (split_k != -1) return stonk_gemm_tn_w4_launch(g, (hipStream_t)stream);
-    return stonk_gemm256_tn_launch(g, (hipStream_t)stream);
+    return split_k == -1 ? stonk_gemm256_tn_launch(g, (hipStream_t)stream) : stonk_gemm_tn_a4_launch(g, (hipStream_t)stream);
   }
   TnArgs a;
   a.A = (const bf16*)dY; a.B = (const bf16*)X; a.C = dW; a.bias = dbias; a.k_dev = k_dev;
   a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.M = M; a.N = N; a.K = K; a.alpha = alpha;
   const int nk = (K + BK - 1) / BK;
   a.split_k = split_k < nk ? split_k : nk;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)gemm_tn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS);
-    attr_done = true;
-  }
   const long tiles = (long)(M / BM) * (N / BN) * a.split_k;
-  hipLaunchKernelGGL(gemm_tn_kernel, dim3((unsigned)tiles), dim3(256), TN_LDS, (hipStream_t)stream, a);
-  return stonk_launch_status();
+  return stonk_gemm::launch_with_lds<gemm_tn_kernel, TN_LDS>(a, (int)tiles, 256, (hipStream_t)stream);
 }

@@ -2,7 +2,7 @@
 // tools/gen_gemm_a4.py -> gemm_a4_loop.inc, STONK_TN_A4_*):
 //   C[M', N'] (fp32) += alpha * sum_t A[t][m] * B[t][n]        A = dY [T, M'], B = X [T, N'], both row-major by token
 //   bias[m]          += alpha * sum_t A[t][m]
-// Same contract as gemm_tn_w4.hip (stonk_gemm_tn_bf16 with split_k == 0 / <= -16 lands here).
+// stonk_gemm_tn_bf16 with split_k == 0 / <= -16 lands here (gemm_tn.hip has the contract).
 //
 // What carries over from the NT kernel: 256 x 256 tiles, four waves (one per SIMD, 128 x 128 wave tiles),
 // v_mfma_f32_16x16x32_bf16 into a[0:255], operands by LDS-DMA two K tiles ahead and across work items, two barriers per
@@ -34,12 +34,6 @@ constexpr int LDS_BYTES = 4 * IMG_BYTES;       // two stages x (A image + B imag
 
 typedef __attribute__((ext_vector_type(4))) int i32x4;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-
-struct Work {
-  int m0, n0;
-  long k_begin;     // first token
-  int nk;           // K tiles (even; tokens past the end read as zeros)
-};
 
 struct Cursor {     // where an operand stream stands: buffer words + bytes left from the base to the end of the live tokens
   i32x4 srd;
@@ -91,7 +85,7 @@ __global__ __launch_bounds__(256, 1) void gemm_tn_a4_kernel(const GemmArgs p) {
     o.k_begin = (long)ks * nk_per * BK;
     int nk = nk_total - ks * nk_per;
     nk = nk < nk_per ? nk : nk_per;
-    o.nk = nk <= 0 ? 0 : nk + (nk & 1);
+    o.nk = nk <= 0 ? 0 : nk + (nk & 1);   // (even; tokens past the end read as zeros)
     return true;
   };
   auto next_work = [&](int& wi, Work& o) -> bool {   // (k_dev may leave a K split empty)
@@ -284,23 +278,12 @@ __global__ __launch_bounds__(256, 1) void gemm_tn_a4_kernel(const GemmArgs p) {
 
 }  // namespace
 
-// weight-gradient form on the written-out loop; a.split_k already chosen, a.flags = grid cap (as gemm_tn_w4.hip)
+// weight-gradient form on the written-out loop; a.split_k already chosen, a.flags = grid cap in CUs (stonk_gemm_tn_bf16)
 int stonk_gemm_tn_a4_launch(const GemmArgs& a, hipStream_t st) {
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return (int)hipGetLastError();
-    n_cu = prop.multiProcessorCount;
-  }
-  static bool attr_done = false;   // (one process per GPU: the attribute is per function and device)
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)gemm_tn_a4_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    attr_done = true;
-  }
+  const int n_cu = cu_count();
+  if (n_cu <= 0) return (int)hipGetLastError();
   const long tiles = (long)((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN) * a.split_k;
   const int cap = (a.flags > 0 && a.flags < n_cu) ? a.flags : n_cu;
   const int grid = (int)(tiles < cap ? tiles : cap);
-  hipLaunchKernelGGL(gemm_tn_a4_kernel, dim3(grid), dim3(256), LDS_BYTES, st, a);
-  return stonk_launch_status();
+  return launch_with_lds<gemm_tn_a4_kernel, LDS_BYTES>(a, grid, 256, st);
 }

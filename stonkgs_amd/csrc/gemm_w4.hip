@@ -43,20 +43,6 @@ constexpr int LDS_BYTES = LDS_RING + 4 * SLAB_BYTES;  // 160 KiB
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 
-struct Work {
-  int m0, n0;       // tile origin
-  long k_begin;     // element offset of the first K tile
-  int nk;           // K tiles in this work item
-};
-
-__device__ __forceinline__ void barrier() { __builtin_amdgcn_s_barrier(); }
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  static_assert(N >= 0 && N <= 63, "vmcnt is six bits");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ void wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
 // VAR: timing experiments only (bit 0 no barrier, bit 2 no global loads / LDS writes in the loop, bit 3 no fragment
 // reads in the loop, bit 4 loads but no LDS writes, bit 5 LDS writes but no loads) - anything but 0 computes garbage.
 // BN_ = 192 (128x96 wave tiles, 4 x 3 MFMA blocks): N = 768 = 4 x 192 tiles the 32 768-row outputs of the step into 512
@@ -518,14 +504,7 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const GemmArgs p) {
 
 template <int OUT_MODE, int EPI, int BN_ = 256>
 int launch_w4(const GemmArgs& a, int grid, hipStream_t st) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)gemm_w4_kernel<OUT_MODE, EPI, BN_>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              LDS_BYTES);
-    attr_done = true;
-  }
-  hipLaunchKernelGGL((gemm_w4_kernel<OUT_MODE, EPI, BN_>), dim3(grid), dim3(256), LDS_BYTES, st, a);
-  return stonk_launch_status();
+  return launch_with_lds<gemm_w4_kernel<OUT_MODE, EPI, BN_>, LDS_BYTES>(a, grid, 256, st);
 }
 
 }  // namespace
@@ -537,29 +516,14 @@ int launch_w4(const GemmArgs& a, int grid, hipStream_t st) {
 // else; the workgroups still take their items in XCD-contiguous runs, and with two items the second one's operands are
 // prefetched across the tile boundary as in the persistent form.
 int stonk_gemm_w4_launch(const GemmArgs& a, int out_mode, int tile_n, int items_per_wg, hipStream_t st) {
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return (int)hipGetLastError();
-    n_cu = prop.multiProcessorCount;
-  }
-  constexpr int B = STONK_EPI_BIAS, G = STONK_EPI_GELU, SV = STONK_EPI_SAVE_PREACT, GB = STONK_EPI_GELU_BWD,
-                R = STONK_EPI_RESID, D = STONK_EPI_DROPOUT, AG = STONK_EPI_AUX_GRAD;
-  const int epi = a.flags & (B | G | SV | GB | R | D | AG);
-  const long ntm = (a.M + BM - 1) / BM;
-  // 192-wide tiles where they quantise better: time ~ rounds of the CUs x tile width (the launches they are built for:
-  // N = 768 at 32 768 rows, two full rounds instead of one and a half; at 16 384 rows one full round instead of 3/4)
-  const bool has192 = out_mode == 0 && a.N % 192 == 0 && (epi == 0 || epi == B || epi == R || epi == (B | R) || epi == (B | R | D));
+  using namespace epi_bits;
+  const int n_cu = cu_count();
+  if (n_cu <= 0) return (int)hipGetLastError();
+  const int epi = a.flags & MASK;
+  const bool has192 = out_mode == 0 && a.N % 192 == 0 && epi_has_192(epi);
   if (tile_n == 192 && !has192) return STONK_ESHAPE;
-  if (tile_n == 0) {
-    const long t256 = ntm * ((a.N + 255) / 256) * a.split_k, t192 = ntm * (a.N / 192) * a.split_k;
-    const long c256 = ((t256 + n_cu - 1) / n_cu) * 256, c192 = ((t192 + n_cu - 1) / n_cu) * 192;
-    tile_n = (has192 && c192 < c256) ? 192 : 256;
-  }
+  const int grid = tile_grid_256(a, has192, a.split_k, items_per_wg, n_cu, tile_n);
   if (tile_n == 192) {
-    const long tiles = ntm * (a.N / 192) * a.split_k;
-    const int grid = (int)(items_per_wg > 0 ? (tiles + items_per_wg - 1) / items_per_wg : (tiles < n_cu ? tiles : n_cu));
     switch (epi) {
       case 0: return launch_w4<0, 0, 192>(a, grid, st);
       case B: return launch_w4<0, B, 192>(a, grid, st);
@@ -568,8 +532,6 @@ int stonk_gemm_w4_launch(const GemmArgs& a, int out_mode, int tile_n, int items_
       default: return launch_w4<0, B | R | D, 192>(a, grid, st);
     }
   }
-  const long tiles = ntm * ((a.N + 255) / 256) * a.split_k;
-  const int grid = (int)(items_per_wg > 0 ? (tiles + items_per_wg - 1) / items_per_wg : (tiles < n_cu ? tiles : n_cu));
   if (out_mode == 1) return epi == 0 ? launch_w4<1, 0>(a, grid, st) : launch_w4<1, -1>(a, grid, st);
   if (out_mode == 2) return launch_w4<2, 0>(a, grid, st);
   switch (epi) {   // the combinations the STonKGs step uses are compiled with constant flags

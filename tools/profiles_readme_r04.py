@@ -71,6 +71,7 @@ Everything below was taken on the round's FINAL code (one `gpurun` call, one box
 | `r04_step_series.log`, `r04_bench_kw.log` | per-step GPU time of a 50-step run (settled from the second step on) and the bench repeated with different K / W on one box (run-to-run spread of one build on one box: 26.3 - 26.8 ms) | `python tools/step_series.py 50`, `bash tools/bench_kw.sh` |
 | `r04_parity_envelopes.log` | what the round's new parity tests print: HIP gradients against the reference's own bf16-autocast gradients (g16 / g17), the HIP loss curves against the reference's fp32 AND bf16 curves (g11 / g12) | `pytest tests/test_shape_true_gpu.py tests/test_losscurve_gpu.py -s -k "real_depth or config5_on_12 or envelope"` |
 | `r04_c4_24L1024_bench.json` | BASELINE config 4 (24L / 1024h / 16 heads / 4096, batch 64) | `python bench.py --full --model 24L1024 --steps 10 --warmup 3 --no-cpu-baseline` |
+| `refactor_gemm_launchers.md` | the GEMM launchers' refactor (one routing step, shared launch helpers, the unreachable compiled four-wave TN kernel removed) against its parent: device code object by object, launch lists under `rocprofv3 --kernel-trace`, results, speed, suites | the commands are in the file |
 
 ## Headline (round 4)
 

@@ -1,6 +1,9 @@
-"""GPU probe of the written-out weight-gradient kernel (gemm_tn_a4.hip) against the compiled four-wave one it replaces:
-parity on the step's shapes, then interleaved timing - on all CUs (split_k = 0 / -2) and held to 160 CUs' worth of workgroups
-(-160 / -2160), as the training step launches it on its second stream."""
+"""GPU probe of the written-out weight-gradient kernel (gemm_tn_a4.hip): parity on the step's shapes, then interleaved timing
+against the eight-wave 256x256 form it is tested beside - on all CUs (split_k = 0) and held to 160 CUs' worth of workgroups
+(-160), as the training step launches it on its second stream.
+  python tools/tn_probe.py [ARM ...]      arms: a4, a4@160, w8 (default: all)
+The compiled four-wave kernel this probe was first written against (arms w4, w4@160) is no longer in the library: asking
+for those arms is an error."""
 import os
 import statistics
 import sys
@@ -18,7 +21,17 @@ def tn(dY, X, dW, db, sk, alpha=1.0, k_dev=None):
              alpha, sk, hip.ptr(k_dev), hip.stream_ptr())
 
 
+ARMS = {"a4": 0, "a4@160": -160, "w8": -1}   # name -> split_k
+REMOVED = ("w4", "w4@160")
+
+
 def main():
+    names = sys.argv[1:] or list(ARMS)
+    for k in names:
+        if k in REMOVED:
+            sys.exit(f"arm {k!r}: the compiled four-wave weight-gradient kernel was removed from the library")
+        if k not in ARMS:
+            sys.exit(f"unknown arm {k!r}: one of {', '.join(ARMS)}")
     hip.lib()
     g = torch.Generator(device="cuda").manual_seed(1)
     T = 26432
@@ -41,7 +54,7 @@ def main():
             print(f"{name} {Mo}x{No} T{T} split_k {sk}: rel dW {e:.2e} db {eb:.2e}{'  <-- FAIL' if bad else ''}", flush=True)
         if not ok:
             break
-        arms = {"a4": 0, "w4": -2, "a4@160": -160, "w4@160": -2160}
+        arms = {k: ARMS[k] for k in names}
         res = {k: [] for k in arms}
         dW = torch.zeros(Mo, No, device="cuda")
         db = torch.zeros(Mo, device="cuda")
