@@ -57,6 +57,14 @@ int stonk_gemm_nt_bf16(const void* A, int64_t lda, const void* B, int64_t ldb, v
  * Autograd's weight/bias gradients of every nn.Linear on the path. */
 int stonk_gemm_tn_bf16(const void* dY, int64_t lda, const void* X, int64_t ldb, float* dW, int64_t ldc, float* dbias,
                        int M, int N, int K, float alpha, int split_k, const int* k_dev, void* stream);
+/* The same product STORED: dW = alpha * dY^T . X, db = alpha * colsum(dY) - whatever dW / db held before is overwritten,
+ * and every element is defined even when *k_dev == 0 (zeros). Only for a launch that stonk_gemm_tn_bf16's routing leaves
+ * with ONE K split (split_k == 1, or a split_k <= 0 whose automatic split comes out as 1; not -1): one producer per
+ * element, so the result equals the accumulating form into zeros bit for bit. Anything else returns STONK_ESHAPE. Also
+ * required: ldc >= N' and M' * ldc * 4 < 2^31 (32-bit byte offsets of the 256x256 kernel's stores), and with split_k <= 0
+ * a bias only when N' <= 256 (that kernel shares the bias sums out over its column tiles), else STONK_ESHAPE. */
+int stonk_gemm_tn_bf16_store(const void* dY, int64_t lda, const void* X, int64_t ldb, float* dW, int64_t ldc, float* dbias,
+                             int M, int N, int K, float alpha, int split_k, const int* k_dev, void* stream);
 
 /* y = dropout(LayerNorm(x)); x,y bf16 [rows,H]; gamma/beta fp32; mean/rstd fp32 [rows] saved for backward.
  * Replaces nn.LayerNorm(eps=1e-12) + nn.Dropout at hf:modeling_bert.py:106-107, :291-292, :349-350, :479. */
@@ -255,6 +263,23 @@ int stonk_adamw_step(float* p, float* g, float* m, float* v, void* p_bf16, int64
                      float eps, float weight_decay, float bias_corr1, float bias_corr2, const float* gnorm_sq_dev,
                      float max_grad_norm, float grad_scale, const int64_t* decay_spans, int n_spans, int64_t span_base,
                      void* stream);
+/* The step over the WHOLE flat buffers (n elements, n % 4 == 0) that also writes the bf16 W^T copies, so that no
+ * stonk_transpose_bf16_batched pass follows it. Bit-identical to stonk_adamw_step (span_base 0) followed by that pass.
+ * tile_desc_dev: device array of n_desc 56-byte entries {int64 off; void* wt; int64 ld_out, rows, prows; int32 cols,
+ * first_tile, col_tiles, pad} sorted by first_tile - a 2-D weight of prows x cols elements at `off` in the flat buffers
+ * (rows <= prows: the logical rows; pad rows are updated but reach the W^T copy as zeros), wt = its [cols, ld_out] copy;
+ * an entry covers ceil(prows/64) * col_tiles tiles of 64x64 (col_tiles = ceil(cols/64)), total_tiles = the sum.
+ * flat_spans_dev: device array of n_flat int64 triples {lo, hi, first_chunk} sorted by first_chunk - every other piece of
+ * [0, n), updated 1024 elements per workgroup (an entry covers ceil((hi - lo)/1024) chunks, total_chunks = the sum).
+ * The caller guarantees what a launcher cannot read from device tables: the two tables cover [0, n) exactly once; off, lo,
+ * hi % 4 == 0; cols % 8 == 0; wt 16-byte aligned, ld_out % 8 == 0, ld_out >= roundup64(rows).
+ * keep_grad_spans (nullable, device): n_keep sorted [lo, hi) ranges whose gradient is left as it is instead of zeroed
+ * (the next step's stonk_gemm_tn_bf16_store overwrites them). decay_spans as for stonk_adamw_step. Tables 8-byte aligned. */
+int stonk_adamw_step_tiled(float* p, float* g, float* m, float* v, void* p_bf16, int64_t n, float lr, float beta1,
+                           float beta2, float eps, float weight_decay, float bias_corr1, float bias_corr2,
+                           const float* gnorm_sq_dev, float max_grad_norm, float grad_scale, const int64_t* decay_spans,
+                           int n_spans, const int64_t* keep_grad_spans, int n_keep, const void* tile_desc_dev, int n_desc,
+                           int total_tiles, const int64_t* flat_spans_dev, int n_flat, int total_chunks, void* stream);
 int stonk_scale_f32(float* x, int64_t n, float s, void* stream);
 
 /* ---- Data-parallel gradient exchange (csrc/comm.hip): RCCL collectives on a stream the LIBRARY owns, handed over by

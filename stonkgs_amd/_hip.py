@@ -32,6 +32,7 @@ LN_DEFER_REDUCE = 1 << 1   # stonk_layernorm_bwd leaves its partial sums for sto
 SMALL_TANH = 1
 SMALL_X_F32 = 16
 LOSS_MSE, LOSS_MSE_BROADCAST, LOSS_BCE = 0, 1, 2
+OK, EINVAL, ESHAPE, EALIGN = 0, -1, -2, -3   # launcher status codes (include/stonk_hip.h)
 ATTN_BWD_DELTA, ATTN_BWD_DQ, ATTN_BWD_DKV, ATTN_BWD_ALL = 1, 2, 4, 7
 
 _vp, _i32, _i64, _f32, _u32 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint32
@@ -41,6 +42,7 @@ _SIGNATURES = {
     "stonk_gemm_nt_bf16": [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _i64,
                            _f32, _i32, _vp, _vp, _f32, _u32, _i32, _vp],
     "stonk_gemm_tn_bf16": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _f32, _i32, _vp, _vp],
+    "stonk_gemm_tn_bf16_store": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _f32, _i32, _vp, _vp],
     "stonk_layernorm_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _i32, _f32, _u32, _vp],
     "stonk_layernorm_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _u32, _f32, _u32,
                             _vp, _i64, _vp],
@@ -80,6 +82,8 @@ _SIGNATURES = {
     "stonk_sumsq_f32": [_vp, _i64, _vp, _vp, _i64, _vp],
     "stonk_adamw_step": [_vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _vp, _f32, _f32,
                          _vp, _i32, _i64, _vp],
+    "stonk_adamw_step_tiled": [_vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _vp, _f32, _f32,
+                               _vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _i32, _i32, _vp],
     "stonk_scale_f32": [_vp, _i64, _f32, _vp],
     # data-parallel gradient exchange: RCCL on a library-owned stream (csrc/comm.hip)
     "stonk_comm_unique_id": [_vp],

@@ -22,6 +22,7 @@
 // persistent 256x256 variant (gemm256.hip, TN = true)
 int stonk_gemm256_tn_launch(const stonk_gemm::GemmArgs& a, hipStream_t st);
 int stonk_gemm_tn_a4_launch(const stonk_gemm::GemmArgs& a, hipStream_t st);
+int stonk_gemm_tn_a4_store_launch(const stonk_gemm::GemmArgs& a, hipStream_t st);   // gemm_tn_a4_store.hip
 
 namespace {
 
@@ -48,6 +49,10 @@ __device__ __forceinline__ int row_swz(int row) { return ((row & 3) << 2) | ((ro
 
 typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
 
+// STORE: the launch has ONE K split, so every output element has exactly one producer - the epilogue writes acc * alpha
+// (and the bias sums) with plain stores instead of adding them into a zeroed buffer, and a launch whose device-side token
+// count leaves no K tile still defines every element (zeros).
+template <bool STORE>
 __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const TnArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
@@ -79,7 +84,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const TnArgs p) {
   const int m0 = rt * BM, n0 = ct * BN;
   int nk = nk_total - ks * nk_per;
   nk = nk < nk_per ? nk : nk_per;
-  if (nk <= 0) return;
+  if (!STORE && nk <= 0) return;
   const long tok_begin = (long)ks * nk_per * BK;
   const bool want_bias = p.bias != nullptr && ct == 0;
 
@@ -156,7 +161,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const TnArgs p) {
     }
   };
 
-  stage(0, 0);
+  if (!STORE || nk > 0) stage(0, 0);
   for (int kt = 0; kt < nk; ++kt) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -173,21 +178,30 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const TnArgs p) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int n = n0 + wn * 64 + j * 16 + (lane & 15);
-        atomicAdd(p.C + (long)m * p.ldc + n, acc[i][j][r] * p.alpha);
+        if constexpr (STORE) p.C[(long)m * p.ldc + n] = acc[i][j][r] * p.alpha;
+        else atomicAdd(p.C + (long)m * p.ldc + n, acc[i][j][r] * p.alpha);
       }
-      if (want_bias && wn == 0 && (lane & 15) == 0) atomicAdd(p.bias + m, accb[i][r] * p.alpha);
+      if (want_bias && wn == 0 && (lane & 15) == 0) {
+        if constexpr (STORE) p.bias[m] = accb[i][r] * p.alpha;
+        else atomicAdd(p.bias + m, accb[i][r] * p.alpha);
+      }
     }
 }
 
 }  // namespace
 
-extern "C" int stonk_gemm_tn_bf16(const void* dY, int64_t lda, const void* X, int64_t ldb, float* dW, int64_t ldc,
-                                  float* dbias, int M, int N, int K, float alpha, int split_k, const int* k_dev,
-                                  void* stream) {
+// shared body of stonk_gemm_tn_bf16 (atomic accumulate) and stonk_gemm_tn_bf16_store (one K split, plain stores)
+static int gemm_tn_route(const void* dY, int64_t lda, const void* X, int64_t ldb, float* dW, int64_t ldc, float* dbias,
+                         int M, int N, int K, float alpha, int split_k, const int* k_dev, void* stream, bool store) {
   STONK_CHECK_ARG(dY && X && dW, STONK_EINVAL);
   STONK_CHECK_ARG(M > 0 && N > 0 && K > 0 && M % BM == 0 && N % BN == 0, STONK_ESHAPE);
   STONK_CHECK_ARG(lda % 8 == 0 && ldb % 8 == 0, STONK_EALIGN);
   STONK_CHECK_ARG((uintptr_t)dY % 16 == 0 && (uintptr_t)X % 16 == 0, STONK_EALIGN);
+  if (store) {
+    // (the 256x256 kernel addresses dW through a buffer resource with 32-bit byte offsets and a byte range of M * ldc * 4)
+    STONK_CHECK_ARG(ldc >= N && (long)M * ldc * 4 < (1L << 31), STONK_ESHAPE);
+    STONK_CHECK_ARG((uintptr_t)dW % 4 == 0 && (uintptr_t)dbias % 4 == 0, STONK_EALIGN);
+  }
   // split_k <= 0: the 256x256 kernels with an automatic split, work items = tiles x splits aimed at one full round of the
   // CUs. 0 (and -2 .. -15): the written-out four-wave kernel (gemm_tn_a4.hip) on all CUs. -16 .. -1024: the same kernel
   // limited to -split_k CUs' worth of workgroups - for launches that run on a second stream beside other work: a persistent
@@ -208,6 +222,12 @@ extern "C" int stonk_gemm_tn_bf16(const void* dY, int64_t lda, const void* X, in
     if (sk > nk / 8) sk = nk / 8 > 0 ? nk / 8 : 1;
     g.split_k = (int)sk;
     g.flags = (int)cus;   // grid cap
+    if (store) {
+      STONK_CHECK_ARG(sk == 1 && split_k != -1, STONK_ESHAPE);
+      // (this kernel shares the bias sums out over the column tiles: one producer per element only with a single one)
+      STONK_CHECK_ARG(!dbias || N <= 256, STONK_ESHAPE);
+      return stonk_gemm_tn_a4_store_launch(g, (hipStream_t)stream);
+    }
     return split_k == -1 ? stonk_gemm256_tn_launch(g, (hipStream_t)stream) : stonk_gemm_tn_a4_launch(g, (hipStream_t)stream);
   }
   TnArgs a;
@@ -216,5 +236,24 @@ extern "C" int stonk_gemm_tn_bf16(const void* dY, int64_t lda, const void* X, in
   const int nk = (K + BK - 1) / BK;
   a.split_k = split_k < nk ? split_k : nk;
   const long tiles = (long)(M / BM) * (N / BN) * a.split_k;
-  return stonk_gemm::launch_with_lds<gemm_tn_kernel, TN_LDS>(a, (int)tiles, 256, (hipStream_t)stream);
+  if (store) {
+    STONK_CHECK_ARG(a.split_k == 1, STONK_ESHAPE);
+    return stonk_gemm::launch_with_lds<gemm_tn_kernel<true>, TN_LDS>(a, (int)tiles, 256, (hipStream_t)stream);
+  }
+  return stonk_gemm::launch_with_lds<gemm_tn_kernel<false>, TN_LDS>(a, (int)tiles, 256, (hipStream_t)stream);
+}
+
+extern "C" int stonk_gemm_tn_bf16(const void* dY, int64_t lda, const void* X, int64_t ldb, float* dW, int64_t ldc,
+                                  float* dbias, int M, int N, int K, float alpha, int split_k, const int* k_dev,
+                                  void* stream) {
+  return gemm_tn_route(dY, lda, X, ldb, dW, ldc, dbias, M, N, K, alpha, split_k, k_dev, stream, false);
+}
+
+// dW = alpha * dY^T . X, db = alpha * colsum(dY): the same kernels with a store epilogue. Only for a launch the routing
+// above leaves UNSPLIT (split_k == 1, or an automatic split that comes out as 1): anything else is refused with
+// STONK_ESHAPE and the caller accumulates with stonk_gemm_tn_bf16 into a zeroed buffer as before.
+extern "C" int stonk_gemm_tn_bf16_store(const void* dY, int64_t lda, const void* X, int64_t ldb, float* dW, int64_t ldc,
+                                        float* dbias, int M, int N, int K, float alpha, int split_k, const int* k_dev,
+                                        void* stream) {
+  return gemm_tn_route(dY, lda, X, ldb, dW, ldc, dbias, M, N, K, alpha, split_k, k_dev, stream, true);
 }

@@ -18,7 +18,23 @@
 //  * bias gradient: one extra MFMA per dY block against an all-ones operand on every ntn-th K tile, into VGPR accumulators;
 //  * tokens past the (device-side) count are out of the buffers' range and arrive as zeros; the cursors carry 64-bit
 //    byte counts (the entity decoder's dlogits are 5.7 GB).
+//
+// STONK_TN_A4_STORE = 1 (gemm_tn_a4_store.hip includes this file with it): the same kernel for launches with ONE K split,
+// where every output element has exactly one producer. The epilogue stores acc * alpha in the same two-rows x 128-byte
+// shape instead of adding it into a zeroed buffer, the bias sums are stored too (the launcher admits a bias only with ONE
+// column tile, where the bias duty below puts every K tile on that tile), and a device-side token count that leaves no K
+// tile makes every work item store zeros.
 #include "gemm_common.h"
+#ifndef STONK_TN_A4_STORE
+#define STONK_TN_A4_STORE 0
+#endif
+#if STONK_TN_A4_STORE
+#define STONK_TN_A4_KERNEL gemm_tn_a4_store_kernel
+#define STONK_TN_A4_LAUNCH stonk_gemm_tn_a4_store_launch
+#else
+#define STONK_TN_A4_KERNEL gemm_tn_a4_kernel
+#define STONK_TN_A4_LAUNCH stonk_gemm_tn_a4_launch
+#endif
 #ifndef STONK_A4_LOOP_INC
 #define STONK_A4_LOOP_INC "gemm_a4_loop.inc"
 #endif
@@ -40,7 +56,7 @@ struct Cursor {     // where an operand stream stands: buffer words + bytes left
   int rem_lo, rem_hi;
 };
 
-__global__ __launch_bounds__(256, 1) void gemm_tn_a4_kernel(const GemmArgs p) {
+__global__ __launch_bounds__(256, 1) void STONK_TN_A4_KERNEL(const GemmArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -60,6 +76,21 @@ __global__ __launch_bounds__(256, 1) void gemm_tn_a4_kernel(const GemmArgs p) {
   const int per_split = ntm * ntn;
   const int total = per_split * p.split_k;
   const int G = gridDim.x;
+#if STONK_TN_A4_STORE
+  if (nk_total == 0) {   // (one K split: every work item is empty) each output tile is defined as zeros, row by row
+    const int ldc0 = (int)p.ldc;
+    for (int w = blockIdx.x; w < total; w += G) {
+      const int rt = ntm >= ntn ? w / ntn : w % ntm, ct = ntm >= ntn ? w % ntn : w / ntm;
+      const int n = ct * BN + tid;
+      for (int r = 0; r < BM; ++r) {
+        const int m = rt * BM + r;
+        if (m < M && n < N) ((float*)p.C)[(long)m * ldc0 + n] = 0.f;
+      }
+      if (p.bias && ct == 0 && rt * BM + tid < M) ((float*)p.bias)[rt * BM + tid] = 0.f;
+    }
+    return;
+  }
+#endif
 
   auto get_work = [&](int w, Work& o) -> bool {
     if (w >= total) return false;
@@ -255,17 +286,31 @@ __global__ __launch_bounds__(256, 1) void gemm_tn_a4_kernel(const GemmArgs p) {
         const int ro = (mrow + e) * ldc_b, ro4 = (mrow + 4 + e) * ldc_b;
 #pragma unroll
         for (int jp = 0; jp < 4; ++jp) {
+#if STONK_TN_A4_STORE
+          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(xs[jp][e] * p.alpha), rC, ro + coff[jp], 0, 0);
+          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(ys[jp][e] * p.alpha), rC, ro4 + coff[jp], 0, 0);
+#else
           __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(xs[jp][e] * p.alpha, rC, ro + coff[jp], 0, 0);
           __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(ys[jp][e] * p.alpha, rC, ro4 + coff[jp], 0, 0);
+#endif
         }
       }
       // bias gradient of this block's 16 features: every column of the extra accumulator holds the same sums
+#if STONK_TN_A4_STORE
+      if (want_bias && wc == 0 && ct == 0) {
+        const int boff = r16 == 0 ? 0 : 0x40000000;   // (one lane per row stores)
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(bacc[i][e] * p.alpha), rBias, (wm0 + 16 * i + 4 * qq + e) * 4 + boff, 0, 0);
+      }
+#else
       if (want_bias && wc == 0) {
         const int boff = r16 == 0 ? 0 : 0x40000000;   // (one lane per row adds)
 #pragma unroll
         for (int e = 0; e < 4; ++e)
           __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(bacc[i][e] * p.alpha, rBias, (wm0 + 16 * i + 4 * qq + e) * 4 + boff, 0, 0);
       }
+#endif
     }
     if (!more) break;
     cwi = nwi;
@@ -279,11 +324,11 @@ __global__ __launch_bounds__(256, 1) void gemm_tn_a4_kernel(const GemmArgs p) {
 }  // namespace
 
 // weight-gradient form on the written-out loop; a.split_k already chosen, a.flags = grid cap in CUs (stonk_gemm_tn_bf16)
-int stonk_gemm_tn_a4_launch(const GemmArgs& a, hipStream_t st) {
+int STONK_TN_A4_LAUNCH(const GemmArgs& a, hipStream_t st) {
   const int n_cu = cu_count();
   if (n_cu <= 0) return (int)hipGetLastError();
   const long tiles = (long)((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN) * a.split_k;
   const int cap = (a.flags > 0 && a.flags < n_cu) ? a.flags : n_cu;
   const int grid = (int)(tiles < cap ? tiles : cap);
-  return launch_with_lds<gemm_tn_a4_kernel, LDS_BYTES>(a, grid, 256, st);
+  return launch_with_lds<STONK_TN_A4_KERNEL, LDS_BYTES>(a, grid, 256, st);
 }

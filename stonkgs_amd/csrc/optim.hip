@@ -77,6 +77,11 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ x,
 // elements, one box): 1, 2 or 4 groups requested per thread before the first use, default or non-temporal accesses -
 // 4.30 / 4.41 / 4.27 TB/s and 4.25 / 4.39 / 4.40: the mix of four read and five write streams runs at 4.3-4.4 TB/s whatever
 // a thread keeps in flight (a plain copy reaches 6.3 on this chip). Two groups, default policy.
+//
+// The training step with replicated optimizer state runs the TILED form further down (stonk_adamw_step_tiled) instead:
+// + 2 bytes for the W^T tile, - 4 where the gradient is not zeroed (the two decoders, 156.8 M parameters, whose next
+// gradient is stored rather than accumulated) - 36 bytes per parameter for a dgrad weight, 32 for the decoders, 33.4 on
+// average over the flagship's 243 M: 8.13 GB, and no separate transpose pass (profiles/optimizer_boundary.md).
 #ifndef STONK_ADAMW_UNROLL
 #define STONK_ADAMW_UNROLL 2
 #endif
@@ -107,22 +112,77 @@ __device__ __forceinline__ void stream_store(T* q, const T& x) {
   *q = x;
 #endif
 }
+// true when element e lies inside one of the n sorted [lo, hi) spans (bisection: last span whose start <= e)
+__device__ __forceinline__ bool in_spans(const long* __restrict__ spans, int n, long e) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (spans[2 * mid] <= e) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo != 0 && e < spans[2 * (lo - 1) + 1];
+}
+
+// The scalars every AdamW kernel derives once per thread, and the update of one group of four elements: ONE definition,
+// so that the flat kernel, its span form and the tiled kernel produce the same bits from the same inputs.
+struct AdamwConsts {
+  float coef, step, inv_sqrt_bc2;
+};
+__device__ __forceinline__ AdamwConsts adamw_consts(float lr, float bc1, float bc2, const float* __restrict__ gnorm_sq,
+                                                    float max_norm, float grad_scale) {
+  AdamwConsts c;
+  c.coef = grad_scale;
+  if (gnorm_sq && max_norm > 0.f) {
+    // torch.nn.utils.clip_grad_norm_: clip_coef = max_norm / (total_norm + 1e-6), clamped to 1
+    const float total = sqrtf(*gnorm_sq) * grad_scale;
+    const float cc = max_norm / (total + 1e-6f);
+    c.coef *= cc < 1.f ? cc : 1.f;
+  }
+  c.step = lr / bc1;
+  c.inv_sqrt_bc2 = rsqrtf(bc2);
+  return c;
+}
+// decoupled weight decay: everywhere (no table), or on the elements inside one of the sorted [lo, hi) spans of the
+// flat buffer (HF Trainer's grouping: weights yes, biases and LayerNorm no). Tensors start at multiples of 256
+// elements, so the four elements of a group share the answer.
+__device__ __forceinline__ float adamw_keep(float lr, float wd, const long* __restrict__ decay_spans, int n_spans, long e) {
+  float keep = 1.f - lr * wd;
+  if (decay_spans && wd != 0.f && !in_spans(decay_spans, n_spans, e)) keep = 1.f;
+  return keep;
+}
+// (Left to -ffp-contract=fast, as the flat kernel always was: which multiply-adds the compiler fuses decides the last bit,
+// and spelling the fusion out by hand did not reproduce the bits the flat kernel has produced so far - tried: m' as
+// fma(1 - b1, g, b1 m), v' as fma(b2, v, (1 - b2) g g), as its instruction stream reads - so the expression stays as it
+// was and tests/test_optim_tiled_gpu.py holds the three kernels to each other bit for bit on every build.)
+__device__ __forceinline__ bf16x4 adamw_update4(f32x4& pp, const f32x4& gg, f32x4& mm, f32x4& vv, const AdamwConsts& c,
+                                                float keep, float b1, float b2, float eps) {
+  bf16x4 o;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float gr = gg[j] * c.coef;
+    float w = pp[j] * keep;
+    mm[j] = b1 * mm[j] + (1.f - b1) * gr;
+    vv[j] = b2 * vv[j] + (1.f - b2) * gr * gr;
+    const float denom = sqrtf(vv[j]) * c.inv_sqrt_bc2 + eps;
+    w -= c.step * (mm[j] / denom);
+    pp[j] = w;
+    o[j] = (bf16)w;
+  }
+  return o;
+}
+
+// `keep_grad` (nullable): sorted [lo, hi) spans of the flat buffer whose gradient is NOT zeroed - the next step's weight
+// gradient overwrites them (store-mode epilogue of the unsplit decoder gradients), so the 4 bytes per parameter of
+// zeroing would be written for nothing.
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, bf16* __restrict__ pb, long n, float lr,
                                                     float b1, float b2, float eps, float wd, float bc1, float bc2,
                                                     const float* __restrict__ gnorm_sq, float max_norm,
                                                     float grad_scale, const long* __restrict__ decay_spans,
-                                                    int n_spans, long span_base) {
+                                                    int n_spans, long span_base, const long* __restrict__ keep_grad,
+                                                    int n_keep) {
   constexpr int U = STONK_ADAMW_UNROLL;
-  float coef = grad_scale;
-  if (gnorm_sq && max_norm > 0.f) {
-    // torch.nn.utils.clip_grad_norm_: clip_coef = max_norm / (total_norm + 1e-6), clamped to 1
-    const float total = sqrtf(*gnorm_sq) * grad_scale;
-    const float c = max_norm / (total + 1e-6f);
-    coef *= c < 1.f ? c : 1.f;
-  }
-  const float step = lr / bc1;
-  const float inv_sqrt_bc2 = rsqrtf(bc2);
+  const AdamwConsts c = adamw_consts(lr, bc1, bc2, gnorm_sq, max_norm, grad_scale);
   const long n4 = n >> 2;
   const long stride = (long)gridDim.x * 256;
   for (long i0 = (long)blockIdx.x * 256 + threadIdx.x; i0 < n4; i0 += stride * U) {
@@ -141,39 +201,47 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
     for (int u = 0; u < U; ++u) {
       const long i = i0 + u * stride;
       if (i >= n4) break;
-      bf16x4 o;
-      // decoupled weight decay: everywhere (no table), or on the elements inside one of the sorted [lo, hi) spans of the
-      // flat buffer (HF Trainer's grouping: weights yes, biases and LayerNorm no). Tensors start at multiples of 256
-      // elements, so the four elements of a group share the answer.
-      float keep = 1.f - lr * wd;
-      if (decay_spans && wd != 0.f) {
-        const long e = span_base + 4 * i;
-        int lo = 0, hi = n_spans;
-        while (lo < hi) {   // last span whose start <= e
-          const int mid = (lo + hi) >> 1;
-          if (decay_spans[2 * mid] <= e) lo = mid + 1;
-          else hi = mid;
-        }
-        if (lo == 0 || e >= decay_spans[2 * (lo - 1) + 1]) keep = 1.f;
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float gr = gg[u][j] * coef;
-        float w = pp[u][j] * keep;
-        mm[u][j] = b1 * mm[u][j] + (1.f - b1) * gr;
-        vv[u][j] = b2 * vv[u][j] + (1.f - b2) * gr * gr;
-        const float denom = sqrtf(vv[u][j]) * inv_sqrt_bc2 + eps;
-        w -= step * (mm[u][j] / denom);
-        pp[u][j] = w;
-        o[j] = (bf16)w;
-      }
+      const float keep = adamw_keep(lr, wd, decay_spans, n_spans, span_base + 4 * i);
+      const bf16x4 o = adamw_update4(pp[u], gg[u], mm[u], vv[u], c, keep, b1, b2, eps);
       stream_store((f32x4*)(p + 4 * i), pp[u]);
       stream_store((f32x4*)(m + 4 * i), mm[u]);
       stream_store((f32x4*)(v + 4 * i), vv[u]);
-      stream_store((f32x4*)(g + 4 * i), (f32x4){0.f, 0.f, 0.f, 0.f});
+      if (!(keep_grad && in_spans(keep_grad, n_keep, span_base + 4 * i)))
+        stream_store((f32x4*)(g + 4 * i), (f32x4){0.f, 0.f, 0.f, 0.f});
       if (pb) *(bf16x4*)(pb + 4 * i) = o;   // (read again by the next forward: default policy)
     }
   }
+}
+
+// The flat update over a device-side list of spans in ONE launch (what the tiled kernel below leaves: biases, LayerNorm,
+// embeddings, pooler, NSP head and the alignment gaps between tensors - about fifty pieces, 1.2 M elements): `spans` =
+// n entries {lo, hi, first_chunk} sorted by first_chunk, a workgroup takes one chunk of 1024 elements of one span.
+constexpr int ADAMW_CHUNK = 1024;
+__global__ __launch_bounds__(256) void adamw_spans_kernel(float* __restrict__ p, float* __restrict__ g,
+                                                          float* __restrict__ m, float* __restrict__ v,
+                                                          bf16* __restrict__ pb, const long* __restrict__ spans, int n,
+                                                          float lr, float b1, float b2, float eps, float wd, float bc1,
+                                                          float bc2, const float* __restrict__ gnorm_sq, float max_norm,
+                                                          float grad_scale, const long* __restrict__ decay_spans,
+                                                          int n_spans, const long* __restrict__ keep_grad, int n_keep) {
+  const long bid = blockIdx.x;
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {   // last entry whose first_chunk <= bid
+    const int mid = (lo + hi + 1) >> 1;
+    if (spans[3 * mid + 2] <= bid) lo = mid;
+    else hi = mid - 1;
+  }
+  const long e = spans[3 * lo] + (bid - spans[3 * lo + 2]) * ADAMW_CHUNK + 4 * threadIdx.x;
+  if (e >= spans[3 * lo + 1]) return;
+  const AdamwConsts c = adamw_consts(lr, bc1, bc2, gnorm_sq, max_norm, grad_scale);
+  f32x4 pp = *(const f32x4*)(p + e), gg = *(const f32x4*)(g + e), mm = *(const f32x4*)(m + e), vv = *(const f32x4*)(v + e);
+  const float keep = adamw_keep(lr, wd, decay_spans, n_spans, e);
+  const bf16x4 o = adamw_update4(pp, gg, mm, vv, c, keep, b1, b2, eps);
+  *(f32x4*)(p + e) = pp;
+  *(f32x4*)(m + e) = mm;
+  *(f32x4*)(v + e) = vv;
+  if (!(keep_grad && in_spans(keep_grad, n_keep, e))) *(f32x4*)(g + e) = (f32x4){0.f, 0.f, 0.f, 0.f};
+  *(bf16x4*)(pb + e) = o;
 }
 
 __global__ __launch_bounds__(256) void scale_kernel(float* __restrict__ x, long n, float s) {
@@ -325,6 +393,84 @@ __global__ __launch_bounds__(256) void transpose_batched_kernel(const TransposeD
   }
 }
 
+// AdamW over the 2-D weights that have a W^T copy, one 64x64 tile per workgroup: the update of adamw_kernel (the same
+// adamw_update4 on the same four-element groups, so the same bits), the row-major bf16 mirror, and - through LDS - the
+// transposed bf16 tile straight into the W^T copy. The separate batched transpose re-read the mirror the optimizer had
+// written microseconds before (0.49 GB in, 0.49 GB out, a launch of its own on the serial path); here the transposed tile
+// costs its 2 bytes per parameter of writes only. `desc` = n entries sorted by first_tile; an entry covers
+// ceil(prows / 64) * col_tiles tiles. prows >= rows are the rows the flat buffers hold (the decoders' pad rows): all of
+// them are updated, rows at or past `rows` reach the W^T copy as zeros up to the tile edge and row tiles past
+// roundup64(rows) do not touch it - exactly what transpose_batched_kernel writes.
+struct AdamwTileDesc {
+  long off;   // first element of the tensor in the flat buffers
+  bf16* wt;
+  long ld_out, rows, prows;
+  int cols, first_tile, col_tiles, pad;
+};
+__global__ __launch_bounds__(256) void adamw_tiled_kernel(float* __restrict__ p, float* __restrict__ g,
+                                                          float* __restrict__ m, float* __restrict__ v,
+                                                          bf16* __restrict__ pb, const AdamwTileDesc* __restrict__ desc,
+                                                          int n, float lr, float b1, float b2, float eps, float wd,
+                                                          float bc1, float bc2, const float* __restrict__ gnorm_sq,
+                                                          float max_norm, float grad_scale,
+                                                          const long* __restrict__ decay_spans, int n_spans,
+                                                          const long* __restrict__ keep_grad, int n_keep) {
+  __shared__ unsigned short tile[TT][TT + 2];
+  const int bid = blockIdx.x;
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {   // last entry whose first_tile <= bid
+    const int mid = (lo + hi + 1) >> 1;
+    if (desc[mid].first_tile <= bid) lo = mid;
+    else hi = mid - 1;
+  }
+  const AdamwTileDesc d = desc[lo];
+  const int tl = bid - d.first_tile;
+  const long r0 = (long)(tl / d.col_tiles) * TT;
+  const int c0 = (tl % d.col_tiles) * TT;
+  const int t = threadIdx.x;
+  const int cc = (t & 15) * 4;   // 16 threads = one 256-byte row segment, 16 rows per pass
+  const bool col_live = c0 + cc < d.cols;
+  const AdamwConsts c = adamw_consts(lr, bc1, bc2, gnorm_sq, max_norm, grad_scale);
+  // (one group of four per trip and NOT unrolled: the compiler then emits for adamw_update4 the instruction sequence it
+  // emits in the flat kernels - unrolled, it paired operations across the trips differently and single results differed in
+  // their last bit; the bitwise test guards this. 59 000 short workgroups keep enough loads in flight without a thread
+  // queueing its own)
+#pragma unroll 1
+  for (int pass = 0; pass < 4; ++pass) {
+    const int rr = (t >> 4) + 16 * pass;
+    const long r = r0 + rr;
+    unsigned short bits[4] = {0, 0, 0, 0};
+    if (col_live && r < d.prows) {
+      const long e = d.off + r * d.cols + c0 + cc;
+      f32x4 pp = *(const f32x4*)(p + e), gg = *(const f32x4*)(g + e), mm = *(const f32x4*)(m + e), vv = *(const f32x4*)(v + e);
+      const float keep = adamw_keep(lr, wd, decay_spans, n_spans, e);
+      const bf16x4 o = adamw_update4(pp, gg, mm, vv, c, keep, b1, b2, eps);
+      *(f32x4*)(p + e) = pp;
+      *(f32x4*)(m + e) = mm;
+      *(f32x4*)(v + e) = vv;
+      if (!(keep_grad && in_spans(keep_grad, n_keep, e))) *(f32x4*)(g + e) = (f32x4){0.f, 0.f, 0.f, 0.f};
+      *(bf16x4*)(pb + e) = o;
+      if (r < d.rows) __builtin_memcpy(bits, &o, 8);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) tile[rr][cc + j] = bits[j];
+  }
+  if (r0 >= d.rows) return;   // (pad rows past the W^T copy's last tile; uniform over the workgroup)
+  __syncthreads();
+  const int oc = t >> 2, rb = (t & 3) * 16;
+  if (c0 + oc < d.cols) {
+    u16x8 o0, o1;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      o0[j] = tile[rb + j][oc];
+      o1[j] = tile[rb + 8 + j][oc];
+    }
+    bf16* dst = d.wt + (long)(c0 + oc) * d.ld_out + r0 + rb;
+    *(u16x8*)dst = o0;
+    *(u16x8*)(dst + 8) = o1;
+  }
+}
+
 inline int ew_grid(long n) {
   long g = (n / 4 + 255) / 256;
   if (g < 1) g = 1;
@@ -358,7 +504,41 @@ extern "C" int stonk_adamw_step(float* p, float* g, float* m, float* v, void* p_
   if (n == 0) return STONK_OK;
   hipLaunchKernelGGL(adamw_kernel, dim3(ew_grid(n) < STONK_ADAMW_BLOCKS ? ew_grid(n) : STONK_ADAMW_BLOCKS), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16*)p_bf16,
                      (long)n, lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, gnorm_sq_dev, max_grad_norm,
-                     grad_scale, (const long*)decay_spans, n_spans, (long)span_base);
+                     grad_scale, (const long*)decay_spans, n_spans, (long)span_base, (const long*)nullptr, 0);
+  return stonk_launch_status();
+}
+
+// The optimizer step of the WHOLE flat buffers with the W^T copies written in the same pass: adamw_tiled_kernel over the
+// tensors of `tile_desc_dev`, adamw_spans_kernel over `flat_spans_dev` = everything else. The tables are device memory the
+// launcher cannot read: the caller guarantees that the two cover [0, n) exactly once, that offsets and span ends are
+// multiples of 4, cols % 8 == 0, W^T copies 16-byte aligned with ld_out % 8 == 0 and ld_out >= roundup64(rows).
+extern "C" int stonk_adamw_step_tiled(float* p, float* g, float* m, float* v, void* p_bf16, int64_t n, float lr,
+                                      float beta1, float beta2, float eps, float weight_decay, float bias_corr1,
+                                      float bias_corr2, const float* gnorm_sq_dev, float max_grad_norm, float grad_scale,
+                                      const int64_t* decay_spans, int n_spans, const int64_t* keep_grad_spans, int n_keep,
+                                      const void* tile_desc_dev, int n_desc, int total_tiles,
+                                      const int64_t* flat_spans_dev, int n_flat, int total_chunks, void* stream) {
+  STONK_CHECK_ARG(p && g && m && v && p_bf16 && n >= 0 && n % 4 == 0, STONK_EINVAL);
+  STONK_CHECK_ARG(n_spans >= 0 && (decay_spans || n_spans == 0) && n_keep >= 0 && (keep_grad_spans || n_keep == 0),
+                  STONK_EINVAL);
+  STONK_CHECK_ARG(tile_desc_dev && n_desc > 0 && total_tiles > 0, STONK_EINVAL);
+  STONK_CHECK_ARG(n_flat >= 0 && total_chunks >= 0 && (n_flat == 0) == (total_chunks == 0) && (flat_spans_dev || n_flat == 0),
+                  STONK_EINVAL);
+  STONK_CHECK_ARG(bias_corr1 > 0.f && bias_corr2 > 0.f, STONK_EINVAL);
+  STONK_CHECK_ARG(((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) % 16 == 0 && (uintptr_t)p_bf16 % 8 == 0,
+                  STONK_EALIGN);
+  STONK_CHECK_ARG(((uintptr_t)tile_desc_dev | (uintptr_t)flat_spans_dev | (uintptr_t)decay_spans |
+                   (uintptr_t)keep_grad_spans) % 8 == 0, STONK_EALIGN);
+  if (n == 0) return STONK_OK;
+  hipLaunchKernelGGL(adamw_tiled_kernel, dim3(total_tiles), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16*)p_bf16,
+                     (const AdamwTileDesc*)tile_desc_dev, n_desc, lr, beta1, beta2, eps, weight_decay, bias_corr1,
+                     bias_corr2, gnorm_sq_dev, max_grad_norm, grad_scale, (const long*)decay_spans, n_spans,
+                     (const long*)keep_grad_spans, n_keep);
+  if (n_flat > 0)
+    hipLaunchKernelGGL(adamw_spans_kernel, dim3(total_chunks), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
+                       (bf16*)p_bf16, (const long*)flat_spans_dev, n_flat, lr, beta1, beta2, eps, weight_decay,
+                       bias_corr1, bias_corr2, gnorm_sq_dev, max_grad_norm, grad_scale, (const long*)decay_spans, n_spans,
+                       (const long*)keep_grad_spans, n_keep);
   return stonk_launch_status();
 }
 

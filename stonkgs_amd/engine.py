@@ -10,6 +10,7 @@ B=64 needs ~12 GB), nothing is recomputed except attention probabilities.
 """
 from __future__ import annotations
 
+import collections
 import contextlib
 
 import math
@@ -134,6 +135,15 @@ class Engine:
         self.marks: Optional[list] = None
         self._wgrad_done: Dict[int, torch.cuda.Event] = {}   # layer parity -> side-stream event after its last wgrad
         self._wt_desc = None   # (device table, entries, tiles) of the batched W^T refresh
+        self._adamw_tables = None   # device tables of stonk_adamw_step_tiled (adamw_tables())
+        # Store-mode weight gradients (stonk_gemm_tn_bf16_store). `store_names`: the weights whose unsplit gradient GEMM may
+        # WRITE its result - set by a trainer whose optimizer then leaves those spans unzeroed; `store_first`: this backward is
+        # the first contribution of the optimizer step (first micro-batch); `grad_stale`: spans that still hold the previous
+        # step's gradient - a launch that cannot store (the routing splits K at this shape) zeroes its span first.
+        self.store_names: tuple = ()
+        self.store_first = False
+        self.grad_stale: set = set()
+        self.store_log = collections.deque(maxlen=64)   # (name, status) of the latest store-mode attempts (tests, debugging)
         self.tn_cus = 160         # CU share of the side-stream weight gradients (tools/sweep_engine_int.py)
         # roctx ranges around the blocks of SURVEY section 2.3 (K1 backbone ... K16 optimizer), so that a
         # `rocprofv3 --marker-trace --kernel-trace` timeline reads by block. Off unless STONK_ROCTX=1 (read once, here).
@@ -276,17 +286,35 @@ class Engine:
             return -self.tn_cus if side_stream else 0
         return max(1, min(32, 480 // tiles, K // 64))
 
-    def wgrad(self, dy, x, dW, db, M_out, N_in, T, k_dev=None, alpha=1.0):
+    def wgrad(self, dy, x, dW, db, M_out, N_in, T, k_dev=None, alpha=1.0, name=None):
         """dW[M_out, N_in] += dy[T, M_out]^T . x[T, N_in];  db[M_out] += colsum(dy)   (fp32 atomics, split-K).
         With `overlap_wgrad` the launch goes to the second stream, ordered after everything enqueued so far on the
-        current one; a GemmTimer brackets it with events on THAT stream, in the same launch configuration."""
+        current one; a GemmTimer brackets it with events on THAT stream, in the same launch configuration.
+        `name` (a weight in `store_names`, first contribution of the optimizer step): the result is STORED when the launch
+        has one K split - no atomics, and the optimizer does not zero the span afterwards."""
         side = self.overlap_wgrad
         split = self._split_k(M_out, N_in, T, side)
         # (the fork: dy and x are complete on the main stream at this point)
         with (self._fork("_wstream") if side else contextlib.nullcontext()), \
                 self._timed("tn_a4" if split <= 0 else "tn", M_out, N_in, T, None, k_dev):
-            hip.call("stonk_gemm_tn_bf16", dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), dW.data_ptr(),
-                     dW.stride(0), hip.ptr(db), M_out, N_in, T, alpha, split, hip.ptr(k_dev), hip.stream_ptr())
+            args = (dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), dW.data_ptr(), dW.stride(0), hip.ptr(db), M_out,
+                    N_in, T, alpha, split, hip.ptr(k_dev), hip.stream_ptr())
+            # what the store entry asks beyond the accumulating one is decided HERE (no bias, ld >= cols, 32-bit byte offsets):
+            # a launch outside it takes the accumulating route by this test, and the entry's STONK_ESHAPE can then only mean
+            # "the routing splits K at this shape" (anything else both entries refuse alike, and the call below raises)
+            can_store = db is None and dW.stride(0) >= N_in and M_out * dW.stride(0) * 4 < 1 << 31
+            if name is not None and self.store_first and name in self.store_names and can_store:
+                rc = hip.lib().stonk_gemm_tn_bf16_store(*args)
+                self.store_log.append((name, rc))
+                if rc == hip.OK:
+                    self.grad_stale.discard(name)
+                    return
+                if rc != hip.ESHAPE:
+                    hip.check(rc, "stonk_gemm_tn_bf16_store")
+            if name in self.grad_stale:   # the optimizer left the previous step's gradient in place
+                dW.zero_()
+                self.grad_stale.discard(name)
+            hip.call("stonk_gemm_tn_bf16", *args)
 
     def _gather_rows(self, src, rd_rows, cnt, dst, cap) -> None:
         """dst[i] = src[rd_rows[i]] for the first cnt[0] rows (a device-side count); rows from the count up to the next
@@ -337,13 +365,10 @@ class Engine:
         desc, n, tiles, _ = self._wt_desc
         hip.call("stonk_transpose_bf16_batched", desc.data_ptr(), n, tiles, st)
 
-    def _build_wt_table(self):
-        """Descriptor table of the batched W^T refresh (stonk_transpose_bf16_batched): one entry per dgrad weight - source =
-        its slice of the bf16 mirror (the optimizer has just written it; bit-identical to casting the fp32 master), destination
-        = the [in, out_padded] copy. Addresses are stable for the life of the store, so the table is built once."""
-        import struct
-
-        entries, first = [], 0
+    def _wt_weights(self):
+        """(name, offset, rows, padded rows, cols, W^T copy) of every weight a dgrad GEMM reads transposed, in the flat
+        buffer's order. The table kernels move 16-byte vectors and cannot validate a device-side table: what they assume is
+        checked here."""
         for name, (off, shape, pshape) in self.P.index.items():
             if len(shape) != 2 or not name.endswith(".weight") or shape[0] < 64:
                 continue
@@ -356,15 +381,55 @@ class Engine:
                 wt = torch.zeros(cols, rpad, dtype=BF16, device=self.device)
                 self.P.wt[name] = wt
             src = self.P.bf16_view(name, padded=False)
-            # the kernel moves 16-byte vectors and cannot validate a device-side table: what it assumes is checked here
-            if cols % 8 or src.data_ptr() % 16 or wt.data_ptr() % 16 or rpad % 8 or wt.shape[1] < (rows + 63) // 64 * 64:
+            if cols % 8 or src.data_ptr() % 16 or wt.data_ptr() % 16 or rpad % 8 or wt.shape[1] < (rows + 63) // 64 * 64 \
+                    or off % 4 or wt.stride(0) != rpad:
                 raise ValueError(f"{name}: [{rows}, {cols}] cannot take the batched W^T refresh (needs cols % 8 == 0, "
                                  "16-byte aligned slices and a destination of roundup64(rows) columns)")
+            yield name, off, rows, pshape[0], cols, rpad, src, wt
+
+    def _build_wt_table(self):
+        """Descriptor table of the batched W^T refresh (stonk_transpose_bf16_batched): one entry per dgrad weight - source =
+        its slice of the bf16 mirror (bit-identical to casting the fp32 master), destination = the [in, out_padded] copy.
+        Addresses are stable for the life of the store, so the table is built once."""
+        import struct
+
+        entries, first = [], 0
+        for name, off, rows, prows, cols, rpad, src, wt in self._wt_weights():
             col_tiles = (cols + 63) // 64
             entries.append(struct.pack("<QQqqqiiii", src.data_ptr(), wt.data_ptr(), cols, rpad, rows, cols, first, col_tiles, 0))
             first += ((rows + 63) // 64) * col_tiles
         raw = torch.frombuffer(bytearray(b"".join(entries)), dtype=torch.uint8).to(self.device)
         return raw, len(entries), first, self.P.bf16.data_ptr()
+
+    def adamw_tables(self):
+        """Device tables of stonk_adamw_step_tiled over the trainable store, built once: (tile descriptors, entries, tiles,
+        flat spans, entries, chunks). The tile table holds the weights of `_wt_weights` (all their padded rows); the flat
+        spans are the complement in [0, numel) - biases, LayerNorm, embeddings, pooler, NSP head and the alignment gaps."""
+        key = (self.P.data.data_ptr(), self.P.bf16.data_ptr())
+        if self._adamw_tables is not None and self._adamw_tables[-1] == key:
+            return self._adamw_tables[:-1]
+        import struct
+
+        entries, first, spans, chunks, pos = [], 0, [], 0, 0
+        for name, off, rows, prows, cols, rpad, src, wt in self._wt_weights():
+            if off < pos or (prows * cols) % 4:
+                raise ValueError(f"{name}: the flat buffer's order or alignment does not fit the tiled optimizer step")
+            if off > pos:
+                spans.append((pos, off, chunks))
+                chunks += (off - pos + 1023) // 1024
+            col_tiles = (cols + 63) // 64
+            entries.append(struct.pack("<qQqqqiiii", off, wt.data_ptr(), rpad, rows, prows, cols, first, col_tiles, 0))
+            first += ((prows + 63) // 64) * col_tiles
+            pos = off + prows * cols
+        if pos < self.P.numel:
+            spans.append((pos, self.P.numel, chunks))
+            chunks += (self.P.numel - pos + 1023) // 1024
+        if not entries or self.P.numel % 4:
+            raise ValueError("no weight with a W^T copy: the tiled optimizer step does not apply")
+        desc = torch.frombuffer(bytearray(b"".join(entries)), dtype=torch.uint8).to(self.device)
+        flat = torch.tensor(spans, dtype=torch.int64, device=self.device).reshape(-1, 3)
+        self._adamw_tables = (desc, len(entries), first, flat, len(spans), chunks, key)
+        return self._adamw_tables[:-1]
 
     # ------------------------------------------------------------------ one BERT layer
     def layer_fwd(self, S: FlatStore, prefix: str, x, B, seq, mask, p_hid, p_att, lidx, save: Optional[dict],
@@ -853,7 +918,7 @@ class Engine:
                           split_k=max(1, min(16, npad // 2048)), m_dev=h["cnt"], alpha=gscale)
             hip.call("stonk_scatter_rows_f32_to_bf16", dhs.data_ptr(), H, h["rows"].data_ptr(), h["cnt"].data_ptr(),
                      dt.data_ptr(), H, H, st)
-            self.wgrad(h["dl"], h["hs"], g_(wname, padded=True), None, npad, H, cap, k_dev=h["cnt"], alpha=gscale)
+            self.wgrad(h["dl"], h["hs"], g_(wname, padded=True), None, npad, H, cap, k_dev=h["cnt"], alpha=gscale, name=wname)
             notify(wname)
         # ---- head transform backward
         dgt = self.buf("b.dgt", (cap_rows, H))

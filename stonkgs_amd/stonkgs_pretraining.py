@@ -138,14 +138,26 @@ class FusedAdamW:
             self._decay_spans = torch.tensor(rows, dtype=torch.int64, device=s.data.device).reshape(-1, 2)
         return self._decay_spans
 
-    def apply_update(self, lr: float, grad_scale: float = 1.0) -> None:
+    def apply_update(self, lr: float, grad_scale: float = 1.0, tables=None, keep_grad=None) -> None:
         """clip (from gnorm_sq) + AdamW + bf16 mirror + gradient zeroing over this rank's pieces. Decoupled weight decay
         (p *= 1 - lr * wd on the decayed tensors only: torch.optim.AdamW's order) happens inside the same kernel, from a
-        device table of the decayed tensors' spans."""
+        device table of the decayed tensors' spans. `tables` (Engine.adamw_tables(); unsharded only): the tiled form, which
+        writes the W^T copies in the same pass - no W^T refresh follows it; `keep_grad` (device [n, 2] int64, sorted): spans
+        whose gradient is left in place for a store-mode weight gradient to overwrite."""
         s, st = self.store, hip.stream_ptr()
         b1, b2 = self.betas
         wd = float(self.weight_decay)
         tab = self._decay_table() if wd else None
+        if tables is not None:
+            if self.spans is not None:
+                raise ValueError("the tiled optimizer step updates the whole flat buffer: not with a sharded optimizer")
+            desc, n_desc, tiles, flat, n_flat, chunks = tables
+            hip.call("stonk_adamw_step_tiled", s.data.data_ptr(), s.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
+                     s.bf16.data_ptr(), s.numel, lr, b1, b2, self.eps, wd, 1.0 - b1 ** self.step_count,
+                     1.0 - b2 ** self.step_count, self.gnorm_sq.data_ptr(), self.max_grad_norm, grad_scale, hip.ptr(tab),
+                     0 if tab is None else tab.shape[0], hip.ptr(keep_grad), 0 if keep_grad is None else keep_grad.shape[0],
+                     desc.data_ptr(), n_desc, tiles, hip.ptr(flat), n_flat, chunks, st)
+            return
         for off, soff, n in self._pieces():
             hip.call("stonk_adamw_step", s.data.data_ptr() + 4 * off, s.grad.data_ptr() + 4 * off,
                      self.m.data_ptr() + 4 * soff, self.v.data_ptr() + 4 * soff, s.bf16.data_ptr() + 2 * off, n, lr, b1, b2,
@@ -442,6 +454,17 @@ class Trainer:
         self.global_step = 0
         self._micro = 0
         self._next_cache = None
+        # Replicated optimizer state: AdamW writes the W^T copies itself (tiled step) and the two decoders' unsplit weight
+        # gradients are stored, not accumulated, by the first micro-batch of a step - so AdamW leaves those spans unzeroed.
+        # A sharded optimizer updates pieces of buckets and zeroes the whole gradient buffer: it keeps the flat path.
+        self._keep_grad = None
+        if not self.sync.shard:
+            names = [n for n in ("cls.predictions.entity_decoder.weight", "cls.predictions.text_decoder.weight")
+                     if n in model._store.index]
+            if names:
+                model.engine.store_names = tuple(names)
+                spans = sorted(model._store.span(n) for n in names)
+                self._keep_grad = torch.tensor(spans, dtype=torch.int64, device=model.device).reshape(-1, 2)
         self.log_history: List[dict] = []
 
     # hf:trainer.py:1892-1963 (+ the optimizer half of :1780-1796 when the accumulation window closes)
@@ -474,8 +497,14 @@ class Trainer:
         last = self._micro % gas == 0
         self.sync.norm_on = bool(self.args.bucket_grad_norm)
         hook = self.sync.on_segment_done if last else None
-        with model.engine.block("K1-K15 forward + backward"):
-            loss = model.forward_backward(inputs, gscale=1.0 / gas, on_segment_done=hook)
+        # (nothing has accumulated into this step's gradients yet: the decoders' weight gradients may be stored. Only for
+        # THIS backward - one that somebody else drives on the same model afterwards accumulates, as autograd expects)
+        model.engine.store_first = gas == 1 or self._micro % gas == 1
+        try:
+            with model.engine.block("K1-K15 forward + backward"):
+                loss = model.forward_backward(inputs, gscale=1.0 / gas, on_segment_done=hook)
+        finally:
+            model.engine.store_first = False
         if last:
             lr = linear_schedule_lr(self.args.learning_rate, self.global_step, self.args.max_steps, self.args.warmup_steps)
             with model.engine.optimizer_stream(self.args.optimizer_overlap), model.engine.block("K16-K17 all-reduce wait + AdamW"):
@@ -485,12 +514,15 @@ class Trainer:
                 if not self.sync.take_grad_norm_sq(opt.gnorm_sq):   # (bucket partials taken during backward)
                     opt.accumulate_grad_norm_sq()           # replicated: the whole buffer; sharded: this rank's pieces ...
                 self.sync.all_reduce_scalar(opt.gnorm_sq)   # ... summed over the ranks (a no-op when replicated)
-                opt.apply_update(lr, grad_scale=scale)
                 if self.sync.shard:
+                    opt.apply_update(lr, grad_scale=scale)
                     model._store.grad.zero_()               # (the kernel zeroed the owned pieces only)
                     self.sync.gather_params(model._store.data)
-                # the W^T copies; sharded: the bf16 mirror of the gathered pieces too
-                model.engine.refresh_derived(bf16_mirror=self.sync.shard)
+                    # the bf16 mirror of the gathered pieces and the W^T copies
+                    model.engine.refresh_derived(bf16_mirror=True)
+                else:   # one pass: update, bf16 mirror, W^T copies; the stored gradients' spans stay as they are
+                    opt.apply_update(lr, grad_scale=scale, tables=model.engine.adamw_tables(), keep_grad=self._keep_grad)
+                    model.engine.grad_stale.update(model.engine.store_names)
             self.global_step += 1
         return loss
 
