@@ -219,6 +219,26 @@ int stonk_softmax_xent_fwd_bwd(const float* logits, int64_t ld, int ncols, int n
 int stonk_softmax_xent_f16_fwd_bwd(const void* logits_f16, int64_t ld, int ncols, int npad, const int* targets,
                                    const int* count_dev, float* loss_sum, void* dlogits, int64_t ld_d, float grad_scale,
                                    int cap_rows, int* err_flag, void* stream);
+
+/* Evaluation / masked prediction on the same label-sparse logits (the reference has no counterpart: it ranks a dense
+ * [B,S,V] tensor in torch, which does not exist here). For every row r < min(*count_dev, cap_rows) - read on the device,
+ * rows at or past it are not written - over the columns [0, ncols) only ([ncols, ld) is the decoder GEMM's padding and
+ * influences nothing), in the total order "larger value first, lower column first among equal values":
+ *   top_idx[r,0..k) / top_val[r,0..k): the k first columns and their RAW logits as fp32 (not log-probabilities);
+ *   lse[r] = log sum exp over the valid columns (fp32, maximum subtracted);
+ *   rank[r] = number of valid columns ordered before targets[r] (zero-based: columns with a larger value, plus columns
+ *   with an equal value and a lower index); tgt_logit[r] = the target's logit.
+ * targets nullable (then rank / tgt_logit are not touched and may be null; otherwise both are required). A target outside
+ * [0, ncols) cannot be refused by the launcher (it lives on the device) and the entry takes no error word: that row gets
+ * rank -1 and tgt_logit NaN, nothing is read out of bounds, and stonk_softmax_xent_* on the same targets - which the
+ * engine runs first - sets bit 3 of its error word. 1 <= k <= 16 and k <= ncols, else STONK_ESHAPE; a null required
+ * pointer or ld < ncols: STONK_EINVAL; both before any launch. Each logit is read once; no workspace, no atomics, the
+ * same input gives the same bits. Rows that are 16-byte aligned (pointer and ld) are read in 16-byte pieces. */
+int stonk_row_topk_f32(const float* logits, int64_t ld, int ncols, const int* targets, const int* count_dev, int cap_rows,
+                       int k, float* top_val, int* top_idx, float* lse, int* rank, float* tgt_logit, void* stream);
+int stonk_row_topk_f16(const void* logits_f16, int64_t ld, int ncols, const int* targets, const int* count_dev,
+                       int cap_rows, int k, float* top_val, int* top_idx, float* lse, int* rank, float* tgt_logit,
+                       void* stream);
 /* NSP loss (ref:stonkgs_model.py:241-243): loss_sum_cnt[0] += sum, [1] += number of labels. */
 int stonk_nsp_xent_fwd_bwd(const float* logits, const int64_t* labels, int B, int C, float* loss_sum_cnt, float* dlogits,
                            float grad_scale, int* err_flag, void* stream);

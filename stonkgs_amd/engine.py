@@ -687,11 +687,14 @@ class Engine:
         return dict(row_of_pos=row_of_pos, pos_of_row=pos_of_row, cu=cu, row_mask=row_mask, read_rows=read_rows,
                     read_of_pos=read_of_pos, cu_rd=cu_rd), ev
 
-    def encode(self, input_ids, attention_mask, token_type_ids, training: bool, save: dict, unpad_labels=None):
+    def encode(self, input_ids, attention_mask, token_type_ids, training: bool, save: dict, unpad_labels=None,
+               layout: Optional[dict] = None):
         """F1-F4: frozen backbone, KG gather + embeddings LayerNorm, encoder layers, pooler. Shared by the pre-training
         and the sequence-classification models (ref:stonkgs_model.py:178-212, ref:stonkgs_finetuning.py:277-310).
         `unpad_labels`: None = padded layout (every position a row: callers that hand out hidden states or dense
-        logits); a (text_labels, entity_labels) pair (either may be None) = packed layout, see `Engine.unpad`."""
+        logits); a (text_labels, entity_labels) pair (either may be None) = packed layout, see `Engine.unpad`.
+        `layout` (a dict, forward-only callers that run heads of their own: `evaluate`): receives the rows of the
+        sequence output (`Th`) and the position -> row map of those rows (`head_map`, None in the padded layout)."""
         cfg = self.cfg
         H, S, half = cfg.hidden_size, cfg.max_position_embeddings, cfg.half_length
         B = input_ids.shape[0]
@@ -785,7 +788,57 @@ class Engine:
                         seq_out=seq_out, pooled=pooled, p_hid=p_hid, p_att=p_att, T=T, rows=rows, plan=plan,
                         first=first, ld_first=ld_first, rd=rd, Th=Th, first_rows=first_rows,
                         head_map=None if plan is None else (plan["row_of_pos"] if rd is None else plan["read_of_pos"]))
+        if layout is not None:
+            layout.update(Th=Th, head_map=None if plan is None else (plan["row_of_pos"] if rd is None else plan["read_of_pos"]))
         return seq_out, pooled
+
+    def _sparse_head(self, pre, nm, wname, N, off, labels, t, row_of_pos, cnt, loss_sum, B, need_backward):
+        """One label-sparse decoder + fused cross-entropy (F6), shared by the training forward (`pre` = "l") and `evaluate`
+        ("ev": small buffers of its own, so that it may run between a forward and its backward): compaction of the labelled
+        positions into rows of `t` (through `row_of_pos` in the packed layout), row gather, decoder GEMM over the
+        device-side count, cross-entropy into `loss_sum` (+ dlogits when `need_backward`). The logits buffer is the same
+        for both callers - nothing reads it after the call that filled it. Returns (rows, targets, cnt, hs, logits, dl)."""
+        H, S, half = self.cfg.hidden_size, self.cfg.max_position_embeddings, self.cfg.half_length
+        cap, npad, st = B * half, pad128(N), hip.stream_ptr()
+        rows = self.buf(f"{pre}.{nm}.rows", (cap,), I32)
+        tg = self.buf(f"{pre}.{nm}.tg", (cap,), I32)
+        hip.call("stonk_label_compact", labels.data_ptr(), cap, half, S, off, rows.data_ptr(), tg.data_ptr(),
+                 cnt.data_ptr(), hip.ptr(row_of_pos), st)
+        hs = self.buf(f"{pre}.{nm}.hs", (cap, H))
+        self._gather_rows(t, rows, cnt, hs, cap)
+        # logits of the labelled rows only, in fp16 (11 significant bits; the softmax arithmetic stays fp32): the
+        # decoder GEMM writes and the cross-entropy reads 2 bytes per logit instead of 4 - both are HBM-bound on them
+        f16 = self.f16_logits
+        logits = self.buf(f"l.{nm}.logits", (cap, npad), torch.float16 if f16 else F32)
+        self.gemm(hs, self.P.bf16_view(wname), logits, cap, npad, H, flags=hip.EPI_OUT_F16 if f16 else hip.EPI_OUT_F32,
+                  m_dev=cnt)
+        dl = self.buf(f"{pre}.{nm}.dl", (cap, npad)) if need_backward else None
+        hip.call("stonk_softmax_xent_f16_fwd_bwd" if f16 else "stonk_softmax_xent_fwd_bwd", logits.data_ptr(), npad,
+                 N, npad, tg.data_ptr(), cnt.data_ptr(), loss_sum.data_ptr(), hip.ptr(dl), npad, 1.0, cap,
+                 self.err.data_ptr(), st)
+        return rows, tg, cnt, hs, logits, dl
+
+    def _head_transform(self, pre, seq_out, pooled, T, B, save_preact: bool):
+        """F4b / F5 on T rows of the sequence output: NSP logits from the pooled vector, then dense + GELU + LayerNorm of
+        the prediction head, in buffers named by `pre` ("h": training forward, "ev": `evaluate`). Returns (nsp, gt, ut, t,
+        stt); `ut` (the saved pre-activation) only with `save_preact`."""
+        cfg = self.cfg
+        H, cap_rows, st = cfg.hidden_size, B * cfg.max_position_embeddings, hip.stream_ptr()
+        f, w = self.P.view, self.P.bf16_view
+        nsp = self.buf(f"{pre}.nsp", (B, 2), F32)
+        hip.call("stonk_small_linear_fwd", pooled.data_ptr(), H, f("cls.seq_relationship.weight").data_ptr(),
+                 f("cls.seq_relationship.bias").data_ptr(), nsp.data_ptr(), B, 2, H, hip.SMALL_X_F32, st)
+        gt = self.buf(f"{pre}.gt", (cap_rows, H))
+        ut = self.buf(f"{pre}.ut", (cap_rows, H)) if save_preact else None
+        self.gemm(seq_out, w("cls.predictions.transform.dense.weight"), gt, T, H, H,
+                  flags=hip.EPI_BIAS | hip.EPI_GELU | (hip.EPI_SAVE_PREACT if save_preact else 0),
+                  bias=f("cls.predictions.transform.dense.bias"), aux=ut)
+        t = self.buf(f"{pre}.t", (cap_rows, H))
+        stt = self.buf(f"{pre}.stt", (2, cap_rows), F32)
+        hip.call("stonk_layernorm_fwd", gt.data_ptr(), f("cls.predictions.transform.LayerNorm.weight").data_ptr(),
+                 f("cls.predictions.transform.LayerNorm.bias").data_ptr(), t.data_ptr(), stt[0].data_ptr(),
+                 stt[1].data_ptr(), T, H, cfg.layer_norm_eps, 0, 0.0, 0, st)
+        return nsp, gt, ut, t, stt
 
     def forward(self, input_ids, attention_mask, token_type_ids, mlm_labels, ent_labels, nsp_labels, training: bool,
                 dense_logits: bool, need_backward: bool, want_hidden: bool = True):
@@ -805,20 +858,8 @@ class Engine:
                                       (mlm_labels, ent_labels) if packed else None)
         T, plan = save["Th"], save["plan"]          # rows of the sequence output: all packed rows, or the read rows
         row_of_pos = save["head_map"]
-        nsp = self.buf("h.nsp", (B, 2), F32)
-        hip.call("stonk_small_linear_fwd", pooled.data_ptr(), H, f("cls.seq_relationship.weight").data_ptr(),
-                 f("cls.seq_relationship.bias").data_ptr(), nsp.data_ptr(), B, 2, H, hip.SMALL_X_F32, st)
         # F5 head transform: dense + GELU, LayerNorm
-        gt = self.buf("h.gt", (cap_rows, H))
-        ut = self.buf("h.ut", (cap_rows, H))
-        self.gemm(seq_out, w("cls.predictions.transform.dense.weight"), gt, T, H, H,
-                  flags=hip.EPI_BIAS | hip.EPI_GELU | hip.EPI_SAVE_PREACT,
-                  bias=f("cls.predictions.transform.dense.bias"), aux=ut)
-        t = self.buf("h.t", (cap_rows, H))
-        stt = self.buf("h.stt", (2, cap_rows), F32)
-        hip.call("stonk_layernorm_fwd", gt.data_ptr(), f("cls.predictions.transform.LayerNorm.weight").data_ptr(),
-                 f("cls.predictions.transform.LayerNorm.bias").data_ptr(), t.data_ptr(), stt[0].data_ptr(),
-                 stt[1].data_ptr(), T, H, cfg.layer_norm_eps, 0, 0.0, 0, st)
+        nsp, gt, ut, t, stt = self._head_transform("h", seq_out, pooled, T, B, True)
         out = dict(hidden_states=seq_out.view(B, S, H) if plan is None else None, pooler_output=pooled, nsp_logits=nsp)
         heads = (("text", "cls.predictions.text_decoder.weight", cfg.vocab_size, 0, mlm_labels),
                  ("ent", "cls.predictions.entity_decoder.weight", cfg.kg_vocab_size, half, ent_labels))
@@ -829,23 +870,8 @@ class Engine:
             cnts = self.buf("l.cnt", (2,), I32)
             cap = B * half
             for hi, (nm, wname, N, off, labels) in enumerate(heads):
-                npad = pad128(N)
-                rows = self.buf(f"l.{nm}.rows", (cap,), I32)
-                tg = self.buf(f"l.{nm}.tg", (cap,), I32)
-                cnt = cnts[hi:hi + 1]
-                hip.call("stonk_label_compact", labels.data_ptr(), cap, half, S, off, rows.data_ptr(), tg.data_ptr(),
-                         cnt.data_ptr(), hip.ptr(row_of_pos), st)
-                hs = self.buf(f"l.{nm}.hs", (cap, H))
-                self._gather_rows(t, rows, cnt, hs, cap)
-                # logits of the labelled rows only, in fp16 (11 significant bits; the softmax arithmetic stays fp32): the
-                # decoder GEMM writes and the cross-entropy reads 2 bytes per logit instead of 4 - both are HBM-bound on them
-                f16 = self.f16_logits
-                logits = self.buf(f"l.{nm}.logits", (cap, npad), torch.float16 if f16 else F32)
-                self.gemm(hs, w(wname), logits, cap, npad, H, flags=hip.EPI_OUT_F16 if f16 else hip.EPI_OUT_F32, m_dev=cnt)
-                dl = self.buf(f"l.{nm}.dl", (cap, npad)) if need_backward else None
-                hip.call("stonk_softmax_xent_f16_fwd_bwd" if f16 else "stonk_softmax_xent_fwd_bwd", logits.data_ptr(), npad,
-                         N, npad, tg.data_ptr(), cnt.data_ptr(), acc[hi:hi + 1].data_ptr(), hip.ptr(dl), npad, 1.0, cap,
-                         self.err.data_ptr(), st)
+                rows, tg, cnt, hs, _, dl = self._sparse_head("l", nm, wname, N, off, labels, t, row_of_pos, cnts[hi:hi + 1],
+                                                             acc[hi:hi + 1], B, need_backward)
                 save[nm] = dict(rows=rows, cnt=cnt, hs=hs, dl=dl)
             dnsp = self.buf("l.dnsp", (B, 2), F32) if need_backward else None
             hip.call("stonk_nsp_xent_fwd_bwd", nsp.data_ptr(), nsp_labels.data_ptr(), B, 2, acc[2:4].data_ptr(),
@@ -874,6 +900,76 @@ class Engine:
         if need_backward:
             save.update(gt=gt, ut=ut, t=t, stt=stt)
             self.saved = save
+        return out
+
+    # ------------------------------------------------------------------ evaluation (forward-only, label-sparse)
+    def evaluate(self, input_ids, attention_mask, token_type_ids, mlm_labels, ent_labels, nsp_labels, k: int = 10):
+        """Held-out evaluation of one batch without dense logits: the training forward's own route - packed encoder rows,
+        last layer on labelled rows + position 0, head transform, stonk_label_compact, row gather, label-sparse decoder
+        GEMM (`m_dev` = the device-side count) into the SAME logits buffers and dtype training uses - with dropout off,
+        the cross-entropy entry called for its loss sums only (null dlogits), and stonk_row_topk_* on the logits it read.
+        Returns device tensors only (views of the workspace, valid until the next call; entries at or past a head's
+        `count` are unspecified): per head ("text", "ent") `rows` (flat b*S + position), `targets`, `count` [1], `top_idx`
+        / `top_val` [cap, k], `lse`, `rank`, `tgt_logit` [cap]; `loss_terms` (total, text, entity, NSP), the four terms by
+        name, `nsp_logits`, `nsp_sum_cnt` (sum of the NSP losses, number of NSP labels).
+        Invisible to training: `saved`, the prefetched frozen-backbone forward and the hint for the next one, the
+        store-mode gradient state, the gradient buffer and the dropout counter are as they were; every buffer a pending
+        backward reads is left alone (own head buffers; the logits buffers are not saved for backward)."""
+        cfg = self.cfg
+        H, S, half = cfg.hidden_size, cfg.max_position_embeddings, cfg.half_length
+        B = input_ids.shape[0]
+        cap_rows, cap = B * S, B * half
+        st = hip.stream_ptr()
+        f, w = self.P.view, self.P.bf16_view
+        # the encoder below must neither consume nor queue a frozen-backbone prefetch, nor advance the dropout counter; it
+        # shares the prefetch's scratch buffers, so it is ordered behind a prefetch in flight
+        held = (self.seed_base, self._prefetch, self.next_input_ids, list(self.rows_executed))
+        self._prefetch = self.next_input_ids = None
+        if held[1] is not None:
+            torch.cuda.current_stream().wait_event(held[1]["done"])
+        layout: dict = {}
+        try:
+            seq_out, pooled = self.encode(input_ids, attention_mask, token_type_ids, False, None, (mlm_labels, ent_labels),
+                                          layout=layout)
+        finally:
+            self.seed_base, self._prefetch, self.next_input_ids = held[:3]
+            self.rows_executed[:] = held[3]
+        T, head_map = layout["Th"], layout["head_map"]
+        nsp, _, _, t, _ = self._head_transform("ev", seq_out, pooled, T, B, False)
+        acc = self.buf("ev.acc", (8,), F32)   # [text_sum, ent_sum, nsp_sum, nsp_cnt, loss x4]
+        acc.zero_()
+        cnts = self.buf("ev.cnt", (2,), I32)
+        out = dict(nsp_logits=nsp)
+        f16 = self.f16_logits
+        for hi, (nm, wname, N, off, labels) in enumerate((
+                ("text", "cls.predictions.text_decoder.weight", cfg.vocab_size, 0, mlm_labels),
+                ("ent", "cls.predictions.entity_decoder.weight", cfg.kg_vocab_size, half, ent_labels))):
+            npad = pad128(N)
+            rows, tg, cnt, _, logits, _ = self._sparse_head("ev", nm, wname, N, off, labels, t, head_map, cnts[hi:hi + 1],
+                                                            acc[hi:hi + 1], B, False)
+            # the caller wants flat positions b*S + off + p; in the packed layout the compaction above produced rows of the
+            # sequence output instead (what the gather reads), so it runs once more without the map: one workgroup, ~20 us
+            pos = rows
+            if head_map is not None:
+                pos = self.buf(f"ev.{nm}.pos", (cap,), I32)
+                hip.call("stonk_label_compact", labels.data_ptr(), cap, half, S, off, pos.data_ptr(), tg.data_ptr(),
+                         cnt.data_ptr(), 0, st)
+            top_val = self.buf(f"ev.{nm}.top_val", (cap, k), F32)
+            top_idx = self.buf(f"ev.{nm}.top_idx", (cap, k), I32)
+            lse = self.buf(f"ev.{nm}.lse", (cap,), F32)
+            rank = self.buf(f"ev.{nm}.rank", (cap,), I32)
+            tl = self.buf(f"ev.{nm}.tgt_logit", (cap,), F32)
+            hip.call("stonk_row_topk_f16" if f16 else "stonk_row_topk_f32", logits.data_ptr(), npad, N, tg.data_ptr(),
+                     cnt.data_ptr(), cap, k, top_val.data_ptr(), top_idx.data_ptr(), lse.data_ptr(), rank.data_ptr(),
+                     tl.data_ptr(), st)
+            out[nm] = dict(rows=pos, targets=tg, count=cnt, top_idx=top_idx, top_val=top_val, lse=lse, rank=rank,
+                           tgt_logit=tl)
+        hip.call("stonk_nsp_xent_fwd_bwd", nsp.data_ptr(), nsp_labels.data_ptr(), B, 2, acc[2:4].data_ptr(), 0, 1.0,
+                 self.err.data_ptr(), st)
+        hip.call("stonk_loss_finalize", acc[0:1].data_ptr(), cnts[0:1].data_ptr(), acc[1:2].data_ptr(),
+                 cnts[1:2].data_ptr(), acc[2:4].data_ptr(), acc[4:8].data_ptr(), st)
+        out.update(loss=acc[4], masked_lm_loss=acc[5], ent_masked_lm_loss=acc[6], next_sentence_loss=acc[7],
+                   loss_terms=acc[4:8], nsp_sum_cnt=acc[2:4])
         return out
 
     # ------------------------------------------------------------------ backward

@@ -477,6 +477,84 @@ class STonKGsForPreTraining(nn.Module):
             return None, pooled.clone()
         return seq_out.view(B, cfg.max_position_embeddings, cfg.hidden_size).clone(), pooled.clone()
 
+    # -------------------------------------------------------------- evaluation / masked prediction (no dense logits)
+    def _prep_long(self, t):
+        if t is None:
+            return None
+        t = torch.as_tensor(t)
+        if t.device != self._device or t.dtype != torch.long or not t.is_contiguous():
+            t = t.to(device=self._device, dtype=torch.long).contiguous()
+        return t
+
+    def _evaluate(self, input_ids, attention_mask, token_type_ids, mlm, elm, nsp, k: int):
+        """Engine.evaluate + the trim to the true label counts: one device-to-host copy (the two counts and the
+        engine's error word) on top of the packed encoder's own wait for its row count."""
+        cfg = self.config
+        S, half = cfg.max_position_embeddings, cfg.half_length
+        if input_ids.dim() != 2 or input_ids.shape[1] != S:
+            raise ValueError(f"input_ids must be [B, {S}] (text half | entity half)")
+        if not 1 <= int(k) <= 16 or k > min(cfg.vocab_size, cfg.kg_vocab_size):
+            raise ValueError("k must be in [1, 16] and at most the smaller vocabulary")
+        self._sync_derived()
+        eng = self.engine
+        out = eng.evaluate(input_ids, attention_mask, token_type_ids, mlm, elm, nsp, int(k))
+        n_text, n_ent, err = torch.cat([out["text"]["count"], out["ent"]["count"], eng.err]).tolist()
+        if err:
+            eng.check_errors()
+        res = {key: out[key].clone() for key in ("loss",) + _TERM_KEYS + ("nsp_logits",)}
+        for nm, n, off in (("text", n_text, 0), ("ent", n_ent, half)):
+            h = out[nm]
+            rows = h["rows"][:n].long()
+            lse = h["lse"][:n]
+            res[nm] = dict(batch_index=rows // S, position=rows % S - off, label=h["targets"][:n].long(),
+                           rank=h["rank"][:n].long(), topk_ids=h["top_idx"][:n].long(),
+                           topk_logprobs=h["top_val"][:n] - lse[:, None], nll=lse - h["tgt_logit"][:n])
+        return res
+
+    @torch.no_grad()
+    def evaluate_batch(self, inputs: Dict[str, torch.Tensor], k: int = 10) -> Dict[str, object]:
+        """Held-out evaluation of one labelled batch (the six schema columns) WITHOUT dense logits: the decoders run on
+        the labelled rows only, as in training, and a top-k kernel reads the logits the loss reads. Works in either
+        module mode; always without dropout and without gradients; leaves no trace in a training run around it.
+
+        Returns `loss`, `masked_lm_loss`, `ent_masked_lm_loss`, `next_sentence_loss` (means over their own labels, as
+        the training loss), `nsp_logits` [B, 2], and under "text" and "ent" one dict per head, rows in row-major order of
+        `labels != -100`, trimmed to the true label count n: `batch_index`, `position` (within the half), `label`, `rank`
+        (zero-based: classes with a larger logit, plus classes with an equal logit and a lower id), `topk_ids` [n, k],
+        `topk_logprobs` [n, k] (logit - logsumexp; non-increasing, ties by lower id) and `nll` [n] (logsumexp - the
+        label's logit). Class ids are in the label space the decoders are trained against - for entities the
+        PREPROCESSING ids 0..K-1 (quirk Q1), not rows of the entity table (`entity_names` maps them)."""
+        t = {key: self._prep_long(v) for key, v in inputs.items()}
+        return self._evaluate(t["input_ids"], t.get("attention_mask"), t.get("token_type_ids"), t["masked_lm_labels"],
+                              t["ent_masked_lm_labels"], t["next_sentence_labels"], k)
+
+    @torch.no_grad()
+    def predict_masked(self, input_ids, attention_mask=None, token_type_ids=None, positions=None, k: int = 10):
+        """"Fill this mask": the k most probable classes at the wanted positions. `positions`: bool [B, S], or None =
+        wherever `input_ids == self.lm_mask_id`, in either half. Returns {"text": (batch_index, position, topk_ids,
+        topk_logprobs), "ent": (...)} - `position` within the half, ids in the decoders' label space (see
+        `evaluate_batch`, whose path this is: labels of 0 at the wanted positions, loss and rank dropped)."""
+        input_ids = self._prep_long(input_ids)
+        half = self.config.half_length
+        want = input_ids == self.lm_mask_id if positions is None else torch.as_tensor(positions).to(self._device) != 0
+        if want.shape != input_ids.shape:
+            raise ValueError("positions must be a bool [B, S] like input_ids")
+        lab = torch.where(want, 0, -100)
+        nsp = torch.zeros(input_ids.shape[0], dtype=torch.long, device=self._device)
+        res = self._evaluate(input_ids, self._prep_long(attention_mask), self._prep_long(token_type_ids),
+                             lab[:, :half].contiguous(), lab[:, half:].contiguous(), nsp, k)
+        return {nm: tuple(res[nm][key] for key in ("batch_index", "position", "topk_ids", "topk_logprobs"))
+                for nm in ("text", "ent")}
+
+    def entity_names(self, ids) -> list:
+        """Names of entity class ids (label space, quirk Q1): id e is the node the model embeds for input id e -
+        `kg_idx_to_name[e]` - and 100 / 102 / 103 are the LM's [UNK] / [SEP] / [MASK] rows. Nested lists in, nested out."""
+        special = {self.lm_unk_id: "[UNK]", self.lm_sep_id: "[SEP]", self.lm_mask_id: "[MASK]"}
+        ids = ids.tolist() if torch.is_tensor(ids) else ids
+        if isinstance(ids, (list, tuple)):
+            return [self.entity_names(i) for i in ids]
+        return special[ids] if ids in special else self.kg_idx_to_name[ids]
+
     # -------------------------------------------------------------- fused training path (no autograd)
     def forward_backward(self, inputs: Dict[str, torch.Tensor], gscale: float = 1.0, on_segment_done=None):
         """forward + hand-written backward in one call: what ``Trainer.training_step`` does through

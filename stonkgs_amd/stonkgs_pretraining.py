@@ -73,6 +73,9 @@ class TrainingArguments:
     # ABI's own communicator (stonk_comm_*: RCCL on a library-owned stream with event hand-off; torch.distributed, if
     # initialised, only carries the 128-byte RCCL id once)
     comm_backend: str = "torch"
+    # held-out evaluation (Trainer.evaluate on `eval_dataset`) every `eval_steps` optimizer steps during train(); 0 = never
+    eval_steps: int = 0
+    per_device_eval_batch_size: int = 8
 
 
 def linear_schedule_lr(base_lr: float, step: int, max_steps: int, warmup: int = 0) -> float:
@@ -426,12 +429,13 @@ class Trainer:
     iterable of already collated batches."""
 
     def __init__(self, model, args: Optional[TrainingArguments] = None, train_dataset=None,
-                 data_collator: Callable = collate):
+                 data_collator: Callable = collate, eval_dataset=None):
         import torch.distributed as dist
 
         self.model = model
         self.args = args or TrainingArguments()
         self.train_dataset = train_dataset
+        self.eval_dataset = eval_dataset
         self.data_collator = data_collator
         self.world = dist.get_world_size() if dist.is_initialized() else 1
         self.rank = dist.get_rank() if dist.is_initialized() else 0
@@ -563,7 +567,69 @@ class Trainer:
                     self.log_history.append({"step": self.global_step, "loss": float(loss), "time": time.time() - t0})
                 if self.args.save_steps and self.global_step % self.args.save_steps == 0:
                     self.save_checkpoint()   # (every rank: a sharded optimizer gathers its state; rank 0 writes)
+                if self.args.eval_steps and self.eval_dataset is not None and self.global_step % self.args.eval_steps == 0:
+                    self.log_history.append({"step": self.global_step, **self.evaluate()})
         return {"global_step": self.global_step, "training_loss": float(loss)}
+
+    # held-out evaluation: no counterpart in the reference's driver (its Trainer gets no eval_dataset); hf:trainer.py evaluate
+    _EVAL_SLOTS = 14   # per head [sum nll, labels, rank 0, rank < k, sum 1/(rank+1)] x 2, NSP [sum nll, labels, correct], rows
+
+    def _eval_batches(self, ds) -> Iterable[Dict[str, torch.Tensor]]:
+        """One pass in the dataset's own order, this rank's share of it, the ragged last batch included."""
+        if isinstance(ds, (list, tuple)) and ds and isinstance(ds[0], dict) and not torch.is_tensor(ds[0]["input_ids"]):
+            bs = self.args.per_device_eval_batch_size
+            shard = list(range(len(ds)))[self.rank::self.world]
+            for i in range(0, len(shard), bs):
+                yield self.data_collator([ds[j] for j in shard[i:i + bs]])
+        else:
+            for i, b in enumerate(ds):
+                if i % self.world == self.rank:
+                    yield b
+
+    def evaluate(self, eval_dataset=None, k: int = 10, max_batches: Optional[int] = None) -> Dict[str, float]:
+        """Loss and ranking metrics over `eval_dataset` (default: the constructor's) through
+        `model.evaluate_batch` - no dense logits, no dropout, nothing a training run around it can notice; the module's
+        mode is left as it is. Every loss term is sum(nll) / sum(labels) over the WHOLE set (not a mean of batch means)
+        and `eval_loss` their sum; per head `acc` = share of labels with rank 0, `hits@k` = share with rank < k, `mrr` =
+        mean 1 / (rank + 1). The sums are kept on the device in fp64 and, in an initialised process group, all-reduced
+        (one 14-element tensor) before dividing. `max_batches` counts the batches of THIS rank (every rank stops after
+        that many of its own share), not batches of the whole set."""
+        import torch.distributed as dist
+
+        ds = self.eval_dataset if eval_dataset is None else eval_dataset
+        if ds is None:
+            raise ValueError("Trainer.evaluate() needs an eval_dataset")
+        model = self.model
+        tot = torch.zeros(self._EVAL_SLOTS, dtype=torch.float64, device=model.device)
+        for i, batch in enumerate(self._eval_batches(ds)):
+            if max_batches is not None and i >= max_batches:
+                break
+            batch = self._on_device(batch)
+            res = model.evaluate_batch(batch, k=k)
+            parts = []
+            for nm in ("text", "ent"):
+                rank = res[nm]["rank"].double()
+                parts += [res[nm]["nll"].double().sum(), rank.new_tensor(float(rank.numel())), (rank == 0).double().sum(),
+                          (rank < k).double().sum(), (1.0 / (rank + 1.0)).sum()]
+            lab, logits = batch["next_sentence_labels"].reshape(-1), res["nsp_logits"].double()
+            live = lab != -100
+            parts += [torch.nn.functional.cross_entropy(logits, lab, reduction="sum"), live.double().sum(),
+                      ((logits.argmax(1) == lab) & live).double().sum(), logits.new_tensor(float(lab.numel()))]
+            tot += torch.stack(parts)
+        if dist.is_initialized():
+            dist.all_reduce(tot, op=dist.ReduceOp.SUM)
+        v = tot.tolist()
+        out, terms = {}, []
+        for nm, key, o in (("text", "masked_lm_loss", 0), ("ent", "ent_masked_lm_loss", 5)):
+            n = max(v[o + 1], 1.0)
+            terms.append(v[o] / n)
+            out[f"eval_{key}"] = v[o] / n
+            out[f"eval_{nm}_acc"], out[f"eval_{nm}_hits@k"], out[f"eval_{nm}_mrr"] = v[o + 2] / n, v[o + 3] / n, v[o + 4] / n
+            out[f"eval_{nm}_labels"] = int(v[o + 1])
+        terms.append(v[10] / max(v[11], 1.0))
+        out.update(eval_next_sentence_loss=terms[2], eval_nsp_acc=v[12] / max(v[11], 1.0), eval_rows=int(v[13]),
+                   eval_loss=sum(terms))
+        return out
 
     # checkpoint / resume (ref:stonkgs_pretraining.py:185-186,196-223: save_steps, save_total_limit, resume)
     def save_checkpoint(self) -> str:
