@@ -161,6 +161,17 @@ int stonk_attention_bwd_phases(int phases, const void* q, const void* k, const v
                                void* dk, int64_t ldd, void* dv, int B, int NH, int S, int D, float scale, float drop_p,
                                uint32_t seed, void* stream);
 
+/* P = softmax(q k^T * scale + key mask), written out. Forward-only, no dropout, PADDED layout only (csrc/attention_probs.hip).
+ * q/k: column slices of the [B*S, 3H] projection (row stride ld), head h at columns h*64.. ; attention_mask int64 [B,S]
+ * (0 = masked key) or NULL. probs (nullable): fp32 [B, NH, S, S], contiguous (HF `attentions` layout), 16-byte aligned.
+ * modal_mass (nullable): fp32 [B, NH, S, 2]: per query row the probability mass on keys [0, half) and [half, S).
+ * At least one of probs / modal_mass; probs == NULL skips the S x S stores. D == 64, S % 128 == 0, 128 <= S <= 4096,
+ * 0 < half < S, half % 64 == 0, scale > 0. The forward kernel's semantics: a masked key gets exactly 0.0, masked positions
+ * as queries still get a row, a sequence without any unmasked key attends uniformly (1/S). Two passes over the keys, no
+ * lse input, no atomics (bitwise reproducible). Replaces hf:modeling_bert.py:111-136 as far as `attention_probs`. */
+int stonk_attention_probs(const void* q, const void* k, int64_t ld, const int64_t* attention_mask, float* probs,
+                          float* modal_mass, int B, int NH, int S, int D, int half, float scale, void* stream);
+
 /* out[c][r] = in[r][c] (bf16). Rows >= *rows_dev (nullable) read as zero; colsum (nullable, fp32) += column sums
  * of `in` (bias gradients). Feeds wgrad operands to stonk_gemm_nt_bf16. */
 int stonk_transpose_bf16(const void* in, int64_t ld_in, void* out, int64_t ld_out, int64_t rows, int cols,

@@ -29,7 +29,8 @@ class STonKGsConfig:
     problem_type: str = None              # None -> inferred from num_labels / label dtype, as the reference does
     # The reference hands `self.bert(...).attentions` through (ref:stonkgs_model.py:256): None unless the HF config says
     # output_attentions. Here the attention probabilities never exist in memory (flash-style kernels keep a row's
-    # running maximum and sum), so a config that asks for them is REFUSED rather than answered with None.
+    # running maximum and sum), so a config that asks for them is REFUSED rather than answered with None; the maps come
+    # from an explicit call, `model.attention_maps(...)`.
     output_attentions: bool = False
 
     @property
@@ -55,7 +56,8 @@ class STonKGsConfig:
         if self.output_attentions:
             raise NotImplementedError(
                 "output_attentions=True: the gfx950 attention kernels never materialise the [B, heads, S, S] probabilities "
-                "(online softmax), so `attentions` cannot be returned; run the reference's CPU path for attention maps")
+                "(online softmax), so a forward never returns `attentions`; call model.attention_maps(...) for them - an "
+                "explicit forward-only pass that writes the selected layers' maps (or only their text / entity mass)")
 
     def update(self, d: dict) -> None:
         for k, v in d.items():

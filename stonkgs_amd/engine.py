@@ -433,11 +433,14 @@ class Engine:
 
     # ------------------------------------------------------------------ one BERT layer
     def layer_fwd(self, S: FlatStore, prefix: str, x, B, seq, mask, p_hid, p_att, lidx, save: Optional[dict],
-                  T: Optional[int] = None, cu=None, rd: Optional[dict] = None):
+                  T: Optional[int] = None, cu=None, rd: Optional[dict] = None, attn_maps: Optional[tuple] = None):
         """One BERT layer on T rows. Padded layout: T = B * seq, `mask` = attention_mask [B, seq]. Packed layout (`cu` =
         sequence offsets of stonk_unpad_plan): T = the packed row count rounded up to 64, `mask` = one word per row.
         `rd` (last layer of the packed layout): the feed-forward block runs on the READ rows only - gathered after the
-        attention block's LayerNorm - and the layer's output has rd["T"] rows."""
+        attention block's LayerNorm - and the layer's output has rd["T"] rows.
+        `attn_maps` (padded layout only): (probs fp32 [B, NH, seq, seq] or None, modal_mass fp32 [B, NH, seq, 2] or None,
+        half) - this layer's attention probabilities at p = 0 are written there (stonk_attention_probs), from the `qkv`
+        buffer right behind the projection: a forward-only pass reuses that buffer from layer to layer."""
         cfg = self.cfg
         H, I, NH = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads
         cap = B * seq
@@ -449,6 +452,12 @@ class Engine:
         qkv = self.buf(f"{tag}.qkv", (cap, 3 * H))
         self.gemm(x, w(prefix + ".attention.self.qkv.weight"), qkv, T, 3 * H, H, flags=hip.EPI_BIAS,
                   bias=f(prefix + ".attention.self.qkv.bias"), kernel=self._kernel("qkv"))
+        if attn_maps is not None:
+            if cu is not None:
+                raise ValueError("attention maps are written in the padded layout only")
+            probs, modal, half = attn_maps
+            hip.call("stonk_attention_probs", qkv.data_ptr(), qkv.data_ptr() + 2 * H, 3 * H, hip.ptr(mask), hip.ptr(probs),
+                     hip.ptr(modal), B, NH, seq, 64, half, 1.0 / math.sqrt(64.0), st)
         # (zeroed when allocated: in the packed layout the rows between the last sequence and T are never written by the
         # attention kernel and must stay finite for the projections that run over them)
         ctx = self.buf(f"{tag}.ctx", (cap, H), zero=True)
@@ -688,17 +697,21 @@ class Engine:
                     read_of_pos=read_of_pos, cu_rd=cu_rd), ev
 
     def encode(self, input_ids, attention_mask, token_type_ids, training: bool, save: dict, unpad_labels=None,
-               layout: Optional[dict] = None):
+               layout: Optional[dict] = None, attn_maps: Optional[dict] = None):
         """F1-F4: frozen backbone, KG gather + embeddings LayerNorm, encoder layers, pooler. Shared by the pre-training
         and the sequence-classification models (ref:stonkgs_model.py:178-212, ref:stonkgs_finetuning.py:277-310).
         `unpad_labels`: None = padded layout (every position a row: callers that hand out hidden states or dense
         logits); a (text_labels, entity_labels) pair (either may be None) = packed layout, see `Engine.unpad`.
         `layout` (a dict, forward-only callers that run heads of their own: `evaluate`): receives the rows of the
-        sequence output (`Th`) and the position -> row map of those rows (`head_map`, None in the padded layout)."""
+        sequence output (`Th`) and the position -> row map of those rows (`head_map`, None in the padded layout).
+        `attn_maps` (forward-only, padded layout, dropout off): {layer index: (probs or None, modal_mass or None)} - the
+        selected layers write their attention probabilities into these tensors (`layer_fwd`)."""
         cfg = self.cfg
         H, S, half = cfg.hidden_size, cfg.max_position_embeddings, cfg.half_length
         B = input_ids.shape[0]
         cap = B * S
+        if attn_maps and (training or save is not None or unpad_labels is not None):
+            raise ValueError("attention maps need a forward-only call in the padded layout with dropout off")
         st = hip.stream_ptr()
         P = self.P
         f = P.view
@@ -767,8 +780,9 @@ class Engine:
         last = cfg.num_hidden_layers - 1
         for i in range(cfg.num_hidden_layers):
             with self.block(f"K4-K8 encoder layer {i} fwd"):
+                am = attn_maps.get(i) if attn_maps else None
                 x = self.layer_fwd(P, f"bert.encoder.layer.{i}", x, B, S, mask, p_hid, p_att, i, save, T=T, cu=cu,
-                                   rd=rd if i == last else None)
+                                   rd=rd if i == last else None, attn_maps=None if am is None else (am[0], am[1], half))
         self._span_end("encoder_fwd", span)
         seq_out = x                                # [Th rows]: every packed row, or the read rows only
         # F4 pooler (fp32 master weights) on position 0 of every sequence
@@ -901,6 +915,22 @@ class Engine:
             save.update(gt=gt, ut=ut, t=t, stt=stt)
             self.saved = save
         return out
+
+    # ------------------------------------------------------------------ attention maps (forward-only, on request)
+    def attention_maps(self, input_ids, attention_mask, token_type_ids, attn_maps: dict):
+        """`encode` in the padded layout, eval mode, with the layers named in `attn_maps` writing their attention
+        probabilities (see `encode`). Returns the pooled output (a workspace view). Invisible to training as `evaluate`
+        is: scratch buffers of its own (save = None), the prefetched frozen-backbone forward, the hint for the next one
+        and the dropout counter are as they were."""
+        held = (self.seed_base, self._prefetch, self.next_input_ids)
+        self._prefetch = self.next_input_ids = None
+        if held[1] is not None:   # (the inline backbone forward shares the prefetch's scratch buffers)
+            torch.cuda.current_stream().wait_event(held[1]["done"])
+        try:
+            _, pooled = self.encode(input_ids, attention_mask, token_type_ids, False, None, None, attn_maps=attn_maps)
+        finally:
+            self.seed_base, self._prefetch, self.next_input_ids = held
+        return pooled
 
     # ------------------------------------------------------------------ evaluation (forward-only, label-sparse)
     def evaluate(self, input_ids, attention_mask, token_type_ids, mlm_labels, ent_labels, nsp_labels, k: int = 10):

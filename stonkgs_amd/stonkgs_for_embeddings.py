@@ -165,3 +165,28 @@ def infer(model: STonKGsForSequenceClassification, data, batch_size: int = 64):
         raw_results.append(r)
         probabilities.append(p)
     return raw_results, probabilities
+
+
+def summarize_modal_mass(modal_mass: torch.Tensor, attention_mask: Optional[torch.Tensor], half: int) -> torch.Tensor:
+    """Who reads whom, per layer and head: ``modal_mass`` fp32 [layers, B, heads, S, 2] (``attention_maps(...,
+    output="modal_mass")``: per query row the probability mass on the text keys [0, half) and on the entity keys
+    [half, S)) -> [layers, heads, 2, 2], entry [l, h, q, k] = the mean mass that the queries of modality q (0 = text,
+    1 = entities) put on the keys of modality k - a mean over the UNMASKED query positions of that half, of all sequences
+    of the batch together (padded positions have a row, but nothing reads it). ``attention_mask`` [B, S] (0 = masked) or
+    None. Each [l, h, q, :] pair sums to 1; a half without any unmasked query gives nan. Host-side analysis glue."""
+    if modal_mass.dim() != 5 or modal_mass.shape[-1] != 2:
+        raise ValueError("modal_mass must be [layers, B, heads, S, 2]")
+    L, B, NH, S, _ = modal_mass.shape
+    if not 0 < half < S:
+        raise ValueError(f"half must be inside (0, {S})")
+    w = torch.ones(B, S, dtype=torch.float64, device=modal_mass.device)
+    if attention_mask is not None:
+        w = (torch.as_tensor(attention_mask).to(modal_mass.device) != 0).to(torch.float64)
+        if w.shape != (B, S):
+            raise ValueError(f"attention_mask must be [{B}, {S}]")
+    mm = modal_mass.to(torch.float64)
+    out = []
+    for sl in (slice(0, half), slice(half, S)):
+        ws = w[:, sl]                                                       # [B, n]
+        out.append(torch.einsum("lbhqk,bq->lhk", mm[:, :, :, sl], ws) / ws.sum())
+    return torch.stack(out, dim=2).to(torch.float32)                        # [L, NH, query modality, key modality]

@@ -477,6 +477,63 @@ class STonKGsForPreTraining(nn.Module):
             return None, pooled.clone()
         return seq_out.view(B, cfg.max_position_embeddings, cfg.hidden_size).clone(), pooled.clone()
 
+    # -------------------------------------------------------------- attention maps (on request only)
+    @torch.no_grad()
+    def attention_maps(self, input_ids, attention_mask=None, token_type_ids=None, layers=None, output: str = "probs",
+                       max_bytes: int = 4 << 30) -> dict:
+        """The encoder's attention probabilities, what the reference hands through as ``outputs.attentions``
+        (ref:stonkgs_model.py:256) - here an explicit forward-only call, because the training and inference kernels never
+        hold the S x S scores. Dropout is OFF (p = 0) in either module mode, which is left as it was: the reference's
+        training-mode ``attentions`` are post-dropout, these are not.
+
+        ``layers``: None = all, or layer indices (negative ones count from the end; no duplicates). ``output``:
+        "probs", "modal_mass" or "both". Returns a dict: ``layers`` (the resolved indices, ascending), ``attentions`` (a
+        tuple of fp32 [B, heads, S, S], one per selected layer, HuggingFace layout; absent for "modal_mass"),
+        ``modal_mass`` (fp32 [len(layers), B, heads, S, 2]: per query row the probability mass on the text half and on the
+        entity half of the keys - see ``stonkgs_for_embeddings.summarize_modal_mass``; absent for "probs") and
+        ``pooler_output`` (fp32 [B, H], as ``encode`` returns it). A masked key has probability exactly 0; padded
+        positions still have a row as queries. The result tensors are allocated up front: more than ``max_bytes`` of them
+        is refused before anything runs."""
+        cfg = self.config
+        S, NH, L = cfg.max_position_embeddings, cfg.num_attention_heads, cfg.num_hidden_layers
+        if output not in ("probs", "modal_mass", "both"):
+            raise ValueError(f'output must be "probs", "modal_mass" or "both" (got {output!r})')
+        wanted = list(range(L)) if layers is None else [int(i) for i in layers]
+        resolved = []
+        for i in wanted:
+            if not -L <= i < L:
+                raise ValueError(f"layer index {i} is out of range for {L} layers")
+            resolved.append(i % L)
+        if len(set(resolved)) != len(resolved):
+            raise ValueError(f"duplicate layer in {wanted}")
+        if not resolved:
+            raise ValueError("no layer selected")
+        resolved = tuple(sorted(resolved))
+        input_ids, attention_mask, token_type_ids = (self._prep_long(t) for t in (input_ids, attention_mask, token_type_ids))
+        if input_ids.dim() != 2 or input_ids.shape[1] != S:
+            raise ValueError(f"input_ids must be [B, {S}] (text half | entity half)")
+        B = input_ids.shape[0]
+        want_p, want_m = output != "modal_mass", output != "probs"
+        need = len(resolved) * B * NH * S * 4 * ((S if want_p else 0) + (2 if want_m else 0))
+        if need > max_bytes:
+            raise ValueError(
+                f"attention_maps would allocate {need} bytes ({need / 2 ** 30:.2f} GiB) for {len(resolved)} layer(s) of "
+                f"[{B}, {NH}, {S}, {S}] fp32, more than max_bytes = {max_bytes}: select fewer layers (layers=...), ask for "
+                'output="modal_mass", or pass a smaller batch')
+        dev = self._device
+        probs = tuple(torch.empty(B, NH, S, S, device=dev, dtype=torch.float32) for _ in resolved) if want_p else None
+        modal = torch.empty(len(resolved), B, NH, S, 2, device=dev, dtype=torch.float32) if want_m else None
+        self._sync_derived()
+        sel = {l: (probs[j] if want_p else None, modal[j] if want_m else None) for j, l in enumerate(resolved)}
+        pooled = self.engine.attention_maps(input_ids, attention_mask, token_type_ids, sel)
+        self.engine.check_errors()
+        res = dict(layers=resolved, pooler_output=pooled.clone())
+        if want_p:
+            res["attentions"] = probs
+        if want_m:
+            res["modal_mass"] = modal
+        return res
+
     # -------------------------------------------------------------- evaluation / masked prediction (no dense logits)
     def _prep_long(self, t):
         if t is None:
