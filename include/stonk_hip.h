@@ -113,6 +113,25 @@ int stonk_text_embed_ln_fwd(const int64_t* input_ids, int64_t ld_ids, const floa
 int stonk_embed_grad(const void* dx, const int64_t* token_type_ids, float* dpos, float* dtype, int B, int S, int H,
                      int type_rows, const int* row_of_pos, void* stream);
 
+/* Input attributions from d F / d(embedding sum) (csrc/input_attribution.hip). The reference has no call for this: the
+ * nearest is autograd with respect to the `inputs_embeds` of ref:src/stonkgs/models/stonkgs_model.py:193-210, which a
+ * reference user reaches only by patching `forward` (the tensor is built inside it from ids). dsum: bf16 [rows, H] with row
+ * stride ld - the input gradient of the embeddings LayerNorm; with dropout off it equals d F / d inputs_embeds, the sum being
+ * inputs_embeds + position + token-type. For padded position p = b*S + s: r = row_of_pos ? row_of_pos[p] : p (row_of_pos
+ * nullable: the packed layout of stonk_unpad_plan); r < 0 (dropped: nothing read the position) writes exactly 0 to all three
+ * outputs; otherwise g = scale * float(dsum[r,:]), x = text_hidden[b*half + s,:] (bf16) for s < half, else
+ * kg_table[input_ids[b,s],:] (fp32), and grad_x_input[p] = sum_h g_h x_h, grad_norm[p] = sqrt(sum_h g_h^2) (fp32 [B*S] each,
+ * at least one non-null), grad_out[p,:] = g (nullable, fp32 [B*S, H] with row stride ld_out, padded layout). An entity id
+ * outside [0, kg_rows) reads no memory and counts as x = 0 (stonk_joint_embed_ln_fwd has set bit 0 of its error word).
+ * fp32 accumulation, one wavefront per position, no atomics, no workspace: bitwise repeatable. Refused before any launch:
+ * a null required pointer or both scalar outputs null (STONK_EINVAL); H % 8, H > 4096, half outside [0, S], kg_rows <= 0,
+ * ld < H, ld_out < H with grad_out (STONK_ESHAPE); dsum / text_hidden / kg_table / grad_out not 16-byte aligned, ld % 8 or
+ * ld_out % 4 (STONK_EALIGN). B == 0 returns STONK_OK. */
+int stonk_input_attribution(const void* dsum, int64_t ld, const int64_t* input_ids, const void* text_hidden,
+                            const float* kg_table, int64_t kg_rows, const int* row_of_pos, float scale,
+                            float* grad_x_input, float* grad_norm, float* grad_out, int64_t ld_out, int B, int S, int half,
+                            int H, void* stream);
+
 /* Row plan of the unpadded trainable encoder. A padded text position is never a key, and its output is read only if it
  * carries a label (the reference labels 15 % of the PADDED half, ref:src/stonkgs/data/indra_for_pretraining.py:33-77) or
  * is position 0 (the pooler's input): every other padded row can be dropped without changing a loss term or a gradient

@@ -144,6 +144,11 @@ class Engine:
         self.store_first = False
         self.grad_stale: set = set()
         self.store_log = collections.deque(maxlen=64)   # (name, status) of the latest store-mode attempts (tests, debugging)
+        # Inputs-only backward (`input_gradients`, which alone sets it): the chain of dgrad GEMMs, LayerNorm and attention
+        # backward runs down to d(embedding sum) and nothing is written to the gradient buffer - `wgrad` returns at once,
+        # `ln_bwd` passes null dgamma / dbeta, the small linear layers' weight gradients go to scratch, stonk_embed_grad
+        # and the `notify` hooks are skipped. False: every path issues exactly the launches it issued before the flag.
+        self._inputs_only = False
         self.tn_cus = 160         # CU share of the side-stream weight gradients (tools/sweep_engine_int.py)
         # roctx ranges around the blocks of SURVEY section 2.3 (K1 backbone ... K16 optimizer), so that a
         # `rocprofv3 --marker-trace --kernel-trace` timeline reads by block. Off unless STONK_ROCTX=1 (read once, here).
@@ -250,6 +255,8 @@ class Engine:
     def ln_bwd(self, dy, x, mean, rstd, gamma, dx, dx_drop, dgamma, dbeta, rows, H, flags, p_in, seed_in, p_out, seed_out):
         """stonk_layernorm_bwd on the current stream, with the shared partial-sum workspace."""
         ws = self.ln_ws()
+        if self._inputs_only:
+            dgamma = dbeta = None
         hip.call("stonk_layernorm_bwd", hip.ptr(dy), hip.ptr(x), hip.ptr(mean), hip.ptr(rstd), hip.ptr(gamma), hip.ptr(dx),
                  hip.ptr(dx_drop), hip.ptr(dgamma), hip.ptr(dbeta), rows, H, flags, p_in, seed_in, p_out, seed_out,
                  ws.data_ptr(), ws.numel(), hip.stream_ptr())
@@ -292,6 +299,8 @@ class Engine:
         current one; a GemmTimer brackets it with events on THAT stream, in the same launch configuration.
         `name` (a weight in `store_names`, first contribution of the optimizer step): the result is STORED when the launch
         has one K split - no atomics, and the optimizer does not zero the span afterwards."""
+        if self._inputs_only:   # (before the store-mode bookkeeping: `store_log`, `grad_stale`, `store_first` do not move)
+            return
         side = self.overlap_wgrad
         split = self._split_k(M_out, N_in, T, side)
         # (the fork: dy and x are complete on the main stream at this point)
@@ -800,18 +809,20 @@ class Engine:
         if save is not None:   # (None: forward-only callers - embedding extraction, batched inference)
             save.update(B=B, attention_mask=mask, token_type_ids=token_type_ids, sum0=sum0, st0=st0,
                         seq_out=seq_out, pooled=pooled, p_hid=p_hid, p_att=p_att, T=T, rows=rows, plan=plan,
-                        first=first, ld_first=ld_first, rd=rd, Th=Th, first_rows=first_rows,
+                        first=first, ld_first=ld_first, rd=rd, Th=Th, first_rows=first_rows, text_hidden=text_hidden,
                         head_map=None if plan is None else (plan["row_of_pos"] if rd is None else plan["read_of_pos"]))
         if layout is not None:
             layout.update(Th=Th, head_map=None if plan is None else (plan["row_of_pos"] if rd is None else plan["read_of_pos"]))
         return seq_out, pooled
 
-    def _sparse_head(self, pre, nm, wname, N, off, labels, t, row_of_pos, cnt, loss_sum, B, need_backward):
+    def _sparse_head(self, pre, nm, wname, N, off, labels, t, row_of_pos, cnt, loss_sum, B, need_backward,
+                     grad_scale: float = 1.0):
         """One label-sparse decoder + fused cross-entropy (F6), shared by the training forward (`pre` = "l") and `evaluate`
         ("ev": small buffers of its own, so that it may run between a forward and its backward): compaction of the labelled
         positions into rows of `t` (through `row_of_pos` in the packed layout), row gather, decoder GEMM over the
         device-side count, cross-entropy into `loss_sum` (+ dlogits when `need_backward`). The logits buffer is the same
-        for both callers - nothing reads it after the call that filled it. Returns (rows, targets, cnt, hs, logits, dl)."""
+        for both callers - nothing reads it after the call that filled it. `grad_scale`: dlogits = (softmax - onehot) *
+        grad_scale / count. Returns (rows, targets, cnt, hs, logits, dl)."""
         H, S, half = self.cfg.hidden_size, self.cfg.max_position_embeddings, self.cfg.half_length
         cap, npad, st = B * half, pad128(N), hip.stream_ptr()
         rows = self.buf(f"{pre}.{nm}.rows", (cap,), I32)
@@ -828,7 +839,7 @@ class Engine:
                   m_dev=cnt)
         dl = self.buf(f"{pre}.{nm}.dl", (cap, npad)) if need_backward else None
         hip.call("stonk_softmax_xent_f16_fwd_bwd" if f16 else "stonk_softmax_xent_fwd_bwd", logits.data_ptr(), npad,
-                 N, npad, tg.data_ptr(), cnt.data_ptr(), loss_sum.data_ptr(), hip.ptr(dl), npad, 1.0, cap,
+                 N, npad, tg.data_ptr(), cnt.data_ptr(), loss_sum.data_ptr(), hip.ptr(dl), npad, grad_scale, cap,
                  self.err.data_ptr(), st)
         return rows, tg, cnt, hs, logits, dl
 
@@ -1002,6 +1013,154 @@ class Engine:
                    loss_terms=acc[4:8], nsp_sum_cnt=acc[2:4])
         return out
 
+    # ------------------------------------------------------------------ input gradients (inputs-only backward)
+    def _attribution_heads(self, sv, heads, dnsp):
+        """Head part of the inputs-only backward of the pre-training model: for every decoder in `heads` (the `save`
+        entries of `_sparse_head`, dlogits = onehot - softmax) dgrad and scatter into d(head transform output), then the
+        head transform's LayerNorm and GELU backward and the dgrad into d(sequence_output); without a decoder that
+        gradient is zero. `dnsp` (fp32 [B, 2] or None): through the NSP classifier into d(pooled). No weight gradient is
+        computed. Returns (dpooled, dseq) for `backward_encoder`."""
+        cfg = self.cfg
+        H, S, half = cfg.hidden_size, cfg.max_position_embeddings, cfg.half_length
+        B, T = sv["B"], sv["Th"]
+        cap_rows, cap = B * S, B * half
+        st = hip.stream_ptr()
+        f, wt = self.P.view, self.P.wt
+        dseq = self.buf("b.dseq", (cap_rows, H))
+        if heads:
+            dt = self.buf("b.dt", (cap_rows, H))[:T]
+            dt.zero_()
+            for wname, N, h in heads:
+                npad = pad128(N)
+                dhs = self.buf("b.dhs32", (cap, H), F32)
+                dhs.zero_()
+                self.gemm(h["dl"], wt[wname], dhs, cap, H, npad, flags=hip.EPI_OUT_F32_ATOMIC,
+                          split_k=max(1, min(16, npad // 2048)), m_dev=h["cnt"])
+                hip.call("stonk_scatter_rows_f32_to_bf16", dhs.data_ptr(), H, h["rows"].data_ptr(), h["cnt"].data_ptr(),
+                         dt.data_ptr(), H, H, st)
+            dgt = self.buf("b.dgt", (cap_rows, H))
+            self.ln_bwd(dt, sv["gt"], sv["stt"][0], sv["stt"][1], f("cls.predictions.transform.LayerNorm.weight"), dgt, None,
+                        None, None, T, H, 0, 0.0, 0, 0.0, 0)
+            dut = self.buf("b.dut", (cap_rows, H))
+            hip.call("stonk_gelu_bwd_bf16", dgt.data_ptr(), sv["ut"].data_ptr(), dut.data_ptr(), T * H, st)
+            self.gemm(dut, wt["cls.predictions.transform.dense.weight"], dseq, T, H, H, kernel=self._kernel("dgrad_head", True))
+        else:
+            dseq[:T].zero_()
+        dpooled = self.buf("b.dpooled", (B, H), F32)
+        if dnsp is not None:
+            dW, db = self._scratch_wgrad(2, H)
+            hip.call("stonk_small_linear_bwd", dnsp.data_ptr(), 0, sv["pooled"].data_ptr(), H,
+                     f("cls.seq_relationship.weight").data_ptr(), dW.data_ptr(), db.data_ptr(), dpooled.data_ptr(), 0, 0, B,
+                     2, H, hip.SMALL_X_F32, st)
+        else:
+            dpooled.zero_()
+        return dpooled, dseq
+
+    def input_gradients(self, input_ids, attention_mask, token_type_ids, grad_x_input, grad_norm, grad_out=None, *,
+                        num_labels: Optional[int] = None, target=None, labels: Optional[dict] = None):
+        """d F / d inputs_embeds per position, reduced by stonk_input_attribution into `grad_x_input` / `grad_norm` (fp32
+        [B, S], either may be None) and written out as `grad_out` (fp32 [B, S, H]) when given. Dropout is off. The forward is
+        the training forward (packed rows of `Engine.unpad`, last layer on the read rows, activations saved); the backward is
+        the training backward's own chain under `_inputs_only`: no weight gradient is computed and the gradient buffer is
+        not touched.
+          classification model (`num_labels`): F_b = logits[b, target_b]; `target` None = the predicted class (one host
+            sync), else int64 [B] on the device. Returns dict(logits, target).
+          pre-training model (`labels`: masked_lm_labels / ent_masked_lm_labels / next_sentence_labels, any non-empty
+            subset): F = sum of log p(label) over the given labels; a head without labels is not run. One host sync for the
+            label counts. Returns dict(score).
+        Returned tensors are workspace views. Between steps the call leaves no trace: the prefetched frozen-backbone
+        forward, the hint for the next one, the dropout counter, `rows_executed`, the store-mode gradient state, the
+        gradient buffer and the parameters are as they were. It uses the training forward's activation buffers, so it refuses
+        to run while a forward is waiting for its backward."""
+        if self.saved is not None:
+            raise RuntimeError("input_gradients() while a training forward is waiting for its backward: the call uses that "
+                               "forward's activation buffers - run the backward first")
+        cfg = self.cfg
+        H, S, half = cfg.hidden_size, cfg.max_position_embeddings, cfg.half_length
+        B = input_ids.shape[0]
+        st = hip.stream_ptr()
+        f = self.P.view
+        counts = {}
+        if num_labels is None:
+            given = {k: v for k, v in (labels or {}).items() if v is not None}
+            if not given:
+                raise ValueError("labels: give at least one of masked_lm_labels, ent_masked_lm_labels, next_sentence_labels")
+            n = torch.stack([(v != -100).sum() for v in given.values()]).tolist()   # (the host sync)
+            counts = {k: c for k, c in zip(given, n) if c > 0}
+            if not counts:
+                raise ValueError("labels: every given label is -100 - there is no prediction to attribute")
+            mlm = given["masked_lm_labels"] if "masked_lm_labels" in counts else None
+            elm = given["ent_masked_lm_labels"] if "ent_masked_lm_labels" in counts else None
+        held = (self.seed_base, self._prefetch, self.next_input_ids, list(self.rows_executed))
+        self._prefetch = self.next_input_ids = None
+        if held[1] is not None:   # (the inline backbone forward shares the prefetch's scratch buffers)
+            torch.cuda.current_stream().wait_event(held[1]["done"])
+        self._inputs_only = True
+        try:
+            save: dict = {}
+            out: dict = {}
+            # (encode orders the stream behind the optimizer's last parameter write before it reads a trainable weight)
+            if num_labels is not None:
+                seq_out, pooled = self.encode(input_ids, attention_mask, token_type_ids, False, save, (None, None))
+                logits = self.buf("ia.logits", (B, num_labels), F32)
+                hip.call("stonk_small_linear_fwd", pooled.data_ptr(), H, f("classifier.weight").data_ptr(),
+                         f("classifier.bias").data_ptr(), logits.data_ptr(), B, num_labels, H, hip.SMALL_X_F32, st)
+                if target is None:
+                    target = logits.argmax(dim=1)
+                dl = self.buf("ia.dl", (B, num_labels), F32)
+                dl.zero_()
+                dl.scatter_(1, target.view(B, 1), 1.0)
+                dpooled = self.buf("b.dpooled", (B, H), F32)
+                dW, db = self._scratch_wgrad(num_labels, H)
+                hip.call("stonk_small_linear_bwd", dl.data_ptr(), 0, pooled.data_ptr(), H, f("classifier.weight").data_ptr(),
+                         dW.data_ptr(), db.data_ptr(), dpooled.data_ptr(), 0, 0, B, num_labels, H, hip.SMALL_X_F32, st)
+                dseq = self.buf("b.dseq", (B * S, H))
+                dseq[:save["Th"]].zero_()   # only position 0 of every sequence receives a gradient (from the pooler)
+                out.update(logits=logits, target=target)
+            else:
+                seq_out, pooled = self.encode(input_ids, attention_mask, token_type_ids, False, save, (mlm, elm))
+                T, head_map = save["Th"], save["head_map"]
+                if mlm is not None or elm is not None:
+                    nsp, gt, ut, t, stt = self._head_transform("h", seq_out, pooled, T, B, True)
+                    save.update(gt=gt, ut=ut, t=t, stt=stt)
+                else:   # NSP labels alone: no decoder runs, so neither does the head transform
+                    t = None
+                    nsp = self.buf("h.nsp", (B, 2), F32)
+                    hip.call("stonk_small_linear_fwd", pooled.data_ptr(), H, f("cls.seq_relationship.weight").data_ptr(),
+                             f("cls.seq_relationship.bias").data_ptr(), nsp.data_ptr(), B, 2, H, hip.SMALL_X_F32, st)
+                acc = self.buf("l.acc", (8,), F32)   # [text_sum, ent_sum, nsp_sum, nsp_cnt, -]
+                acc.zero_()
+                cnts = self.buf("l.cnt", (2,), I32)
+                heads = []
+                for hi, (nm, key, wname, N, off, lab) in enumerate((
+                        ("text", "masked_lm_labels", "cls.predictions.text_decoder.weight", cfg.vocab_size, 0, mlm),
+                        ("ent", "ent_masked_lm_labels", "cls.predictions.entity_decoder.weight", cfg.kg_vocab_size, half, elm))):
+                    if lab is None:
+                        continue
+                    # (softmax - onehot) * grad_scale / count with grad_scale = -count: onehot - softmax, d log p / d logits
+                    rows, tg, cnt, hs, _, dl = self._sparse_head("l", nm, wname, N, off, lab, t, head_map, cnts[hi:hi + 1],
+                                                                 acc[hi:hi + 1], B, True, grad_scale=-float(counts[key]))
+                    heads.append((wname, N, dict(rows=rows, cnt=cnt, dl=dl)))
+                dnsp = None
+                if "next_sentence_labels" in counts:
+                    dnsp = self.buf("l.dnsp", (B, 2), F32)
+                    hip.call("stonk_nsp_xent_fwd_bwd", nsp.data_ptr(), given["next_sentence_labels"].data_ptr(), B, 2,
+                             acc[2:4].data_ptr(), dnsp.data_ptr(), -float(counts["next_sentence_labels"]),
+                             self.err.data_ptr(), st)
+                dpooled, dseq = self._attribution_heads(save, heads, dnsp)
+                out.update(score=-acc[0:3].sum())
+            dsum = self.backward_encoder(dpooled, dseq, save, None)
+            plan = save["plan"]
+            hip.call("stonk_input_attribution", dsum.data_ptr(), dsum.stride(0), input_ids.data_ptr(),
+                     save["text_hidden"].data_ptr(), self.kg_table.data_ptr(), self.kg_table.shape[0],
+                     0 if plan is None else plan["row_of_pos"].data_ptr(), 1.0, hip.ptr(grad_x_input), hip.ptr(grad_norm),
+                     hip.ptr(grad_out), H, B, S, half, H, st)
+        finally:
+            self._inputs_only = False
+            self.seed_base, self._prefetch, self.next_input_ids = held[:3]
+            self.rows_executed[:] = held[3]
+        return out
+
     # ------------------------------------------------------------------ backward
     def backward(self, gscale: float = 1.0, on_segment_done: Optional[Callable[[str], None]] = None) -> None:
         """Accumulate d(loss * gscale)/d(param) into the flat gradient buffer. `on_segment_done(name)` fires as
@@ -1067,6 +1226,12 @@ class Engine:
                  g_("cls.seq_relationship.bias").data_ptr(), dpooled.data_ptr(), 0, 0, B, 2, H, hip.SMALL_X_F32, st)
         self.backward_encoder(dpooled, dseq, sv, notify)
 
+    def _scratch_wgrad(self, N: int, K: int):
+        """(inputs-only backward) somewhere for stonk_small_linear_bwd to put the dW [N, K] / db [N] it cannot be told to
+        skip: one scratch buffer, never read."""
+        w = self.buf("ia.dw", (N * K + N,), F32)
+        return w[:N * K], w[N * K:]
+
     def _make_notify(self, hook):
         """Gradients of a segment are final once the SIDE stream has run its weight-gradient GEMMs: the DP hook (RCCL
         all-reduce) is therefore issued under the side stream, which it then orders itself after."""
@@ -1089,8 +1254,11 @@ class Engine:
             torch.cuda.current_stream().wait_stream(self._wstream)
         self._wgrad_done.clear()
 
-    def backward_encoder(self, dpooled, dseq, sv, notify) -> None:
-        """Pooler (tanh) backward into position 0 of d(sequence_output), encoder layers last to first, embeddings."""
+    def backward_encoder(self, dpooled, dseq, sv, notify):
+        """Pooler (tanh) backward into position 0 of d(sequence_output), encoder layers last to first, embeddings.
+        Returns `dsum`, the gradient of the embedding sum (bf16, the forward's row layout; a workspace view)."""
+        if self._inputs_only:
+            notify = lambda name: None   # noqa: E731
         cfg = self.cfg
         H, S = cfg.hidden_size, cfg.max_position_embeddings
         B = sv["B"]
@@ -1105,9 +1273,11 @@ class Engine:
             nb.fill_(B)
             acc, ld_acc = self.buf("b.dfirst", ((B + 127) // 128 * 128, H)), H
             self._gather_rows(dseq, first_rows, nb, acc, acc.shape[0])
+        dWp, dbp = (g_("bert.pooler.dense.weight"), g_("bert.pooler.dense.bias")) if not self._inputs_only \
+            else self._scratch_wgrad(H, H)
         hip.call("stonk_small_linear_bwd", dpooled.data_ptr(), sv["pooled"].data_ptr(), sv["first"].data_ptr(),
-                 sv["ld_first"], f("bert.pooler.dense.weight").data_ptr(), g_("bert.pooler.dense.weight").data_ptr(),
-                 g_("bert.pooler.dense.bias").data_ptr(), 0, acc.data_ptr(), ld_acc, B, H, H, hip.SMALL_TANH, st)
+                 sv["ld_first"], f("bert.pooler.dense.weight").data_ptr(), dWp.data_ptr(), dbp.data_ptr(), 0,
+                 acc.data_ptr(), ld_acc, B, H, H, hip.SMALL_TANH, st)
         if plan is not None:
             hip.call("stonk_scatter_rows_bf16", acc.data_ptr(), H, first_rows.data_ptr(), nb.data_ptr(), dseq.data_ptr(), H,
                      H, st)
@@ -1135,13 +1305,15 @@ class Engine:
         self.ln_bwd(dy, sv["sum0"], sv["st0"][0], sv["st0"][1], f("bert.embeddings.LayerNorm.weight"), dsum, None,
                     g_("bert.embeddings.LayerNorm.weight"), g_("bert.embeddings.LayerNorm.bias"), T, H,
                     hip.LN_DROPOUT if p_hid > 0 else 0, p_hid, self.seed(200, 0), 0.0, 0)
-        hip.call("stonk_embed_grad", dsum.data_ptr(), hip.ptr(sv["token_type_ids"]),
-                 g_("bert.embeddings.position_embeddings.weight").data_ptr(),
-                 g_("bert.embeddings.token_type_embeddings.weight").data_ptr(), B, S, H, cfg.type_vocab_size,
-                 0 if plan is None else plan["row_of_pos"].data_ptr(), st)
+        if not self._inputs_only:
+            hip.call("stonk_embed_grad", dsum.data_ptr(), hip.ptr(sv["token_type_ids"]),
+                     g_("bert.embeddings.position_embeddings.weight").data_ptr(),
+                     g_("bert.embeddings.token_type_embeddings.weight").data_ptr(), B, S, H, cfg.type_vocab_size,
+                     0 if plan is None else plan["row_of_pos"].data_ptr(), st)
         notify("bert.embeddings")
         self.mark("backward_end")
         self.join_wgrad()
+        return dsum
 
     # ------------------------------------------------------------------ sequence classification head (config 5)
     def forward_cls(self, input_ids, attention_mask, token_type_ids, labels, num_labels: int, training: bool,

@@ -190,3 +190,27 @@ def summarize_modal_mass(modal_mass: torch.Tensor, attention_mask: Optional[torc
         ws = w[:, sl]                                                       # [B, n]
         out.append(torch.einsum("lbhqk,bq->lhk", mm[:, :, :, sl], ws) / ws.sum())
     return torch.stack(out, dim=2).to(torch.float32)                        # [L, NH, query modality, key modality]
+
+
+def summarize_attributions(attr: torch.Tensor, attention_mask: Optional[torch.Tensor], half: int, top: int = 10) -> dict:
+    """Evidence or graph, and where exactly: ``attr`` [B, S] (``grad_x_input`` or ``grad_norm`` of
+    ``model.input_attributions``) -> per sequence ``shares`` fp32 [B, 2]: the share of sum |attr| on the UNMASKED text
+    positions [0, half) and on the entity positions [half, S) - masked text positions are left out of both, so the two
+    shares sum to 1 (nan for a sequence whose counted attributions are all zero) - and the ``top`` positions by |attr|
+    over the whole sequence, largest first: ``top_positions`` int64 [B, top] and ``top_values`` [B, top] (the signed
+    values there; ``top`` is cut to S). ``attention_mask`` [B, S] (0 = masked) or None. Host-side analysis glue."""
+    if attr.dim() != 2:
+        raise ValueError("attr must be [B, S]")
+    B, S = attr.shape
+    if not 0 < half < S:
+        raise ValueError(f"half must be inside (0, {S})")
+    a = attr.to(torch.float64).abs()
+    w = torch.ones(B, S, dtype=torch.float64, device=attr.device)
+    if attention_mask is not None:
+        w = (torch.as_tensor(attention_mask).to(attr.device) != 0).to(torch.float64)
+        if w.shape != (B, S):
+            raise ValueError(f"attention_mask must be [{B}, {S}]")
+    text, ent = (a[:, :half] * w[:, :half]).sum(1), a[:, half:].sum(1)
+    shares = (torch.stack([text, ent], dim=1) / (text + ent)[:, None]).to(torch.float32)
+    idx = a.topk(min(int(top), S), dim=1).indices
+    return dict(shares=shares, top_positions=idx, top_values=attr.gather(1, idx))

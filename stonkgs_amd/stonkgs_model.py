@@ -534,6 +534,61 @@ class STonKGsForPreTraining(nn.Module):
             res["modal_mass"] = modal
         return res
 
+    # -------------------------------------------------------------- input attributions (on request only)
+    def _attribution_buffers(self, input_ids, return_gradient: bool, max_bytes: int):
+        """Shape check and the result tensors of `input_attributions`, allocated up front."""
+        cfg = self.config
+        S, H = cfg.max_position_embeddings, cfg.hidden_size
+        if input_ids.dim() != 2 or input_ids.shape[1] != S:
+            raise ValueError(f"input_ids must be [B, {S}] (text half | entity half)")
+        B = input_ids.shape[0]
+        need = B * S * H * 4 if return_gradient else 0
+        if need > max_bytes:
+            raise ValueError(f"return_gradient would allocate {need} bytes ({need / 2 ** 30:.2f} GiB) for [{B}, {S}, {H}] "
+                             f"fp32, more than max_bytes = {max_bytes}: pass a smaller batch or raise max_bytes")
+        dev = self._device
+        gxi = torch.empty(B, S, device=dev, dtype=torch.float32)
+        gn = torch.empty(B, S, device=dev, dtype=torch.float32)
+        grad = torch.empty(B, S, H, device=dev, dtype=torch.float32) if return_gradient else None
+        return gxi, gn, grad
+
+    @torch.no_grad()
+    def input_attributions(self, input_ids, attention_mask=None, token_type_ids=None, labels=None,
+                           return_gradient: bool = False, max_bytes: int = 1 << 30) -> dict:
+        """Which evidence tokens and which walk entities drive a masked prediction: the gradient of
+        F = sum of log p(label) with respect to the input embeddings (the `inputs_embeds` of ref:stonkgs_model.py:193-210:
+        the frozen backbone's output for the text half, the entity table's rows for the other), per position.
+
+        ``labels``: a dict with any non-empty subset of ``masked_lm_labels`` [B, S/2], ``ent_masked_lm_labels`` [B, S/2],
+        ``next_sentence_labels`` [B]; F sums over the labels that are not -100. Sequences are independent: row b of the
+        result is the gradient of sequence b's own terms. Returns ``score`` (fp32 scalar tensor: F), ``grad_x_input``
+        (fp32 [B, S]: <dF/dx_p, x_p>), ``grad_norm`` (fp32 [B, S]: |dF/dx_p|, saliency) and, with ``return_gradient``,
+        ``gradient`` (fp32 [B, S, H]; allocated up front, refused beyond ``max_bytes``). A padded position that carries no
+        label and is not position 0 is read by nothing: its entries are exactly 0.
+
+        Dropout is off in either module mode, which is left as it was; no parameter gradient is computed and a training
+        run around the call does not notice it (Engine.input_gradients) - but it may not run between a training-mode
+        forward and its backward (RuntimeError). See ``stonkgs_for_embeddings.summarize_attributions``."""
+        names = ("masked_lm_labels", "ent_masked_lm_labels", "next_sentence_labels")
+        if labels is not None and set(labels) - set(names):
+            raise ValueError(f"labels: unknown key(s) {sorted(set(labels) - set(names))}; expected a subset of {names}")
+        lab = {k: self._prep_long(v) for k, v in (labels or {}).items() if v is not None}
+        if not lab:
+            raise ValueError(f"labels: give a dict with at least one of {names}")
+        input_ids, attention_mask, token_type_ids = (self._prep_long(t) for t in (input_ids, attention_mask, token_type_ids))
+        gxi, gn, grad = self._attribution_buffers(input_ids, return_gradient, max_bytes)
+        B, half = input_ids.shape[0], self.config.half_length
+        for k, v in lab.items():
+            if (v.numel() != B) if k == "next_sentence_labels" else (tuple(v.shape) != (B, half)):
+                raise ValueError(f"labels[{k!r}] must have shape {(B,) if k == 'next_sentence_labels' else (B, half)}")
+        self._sync_derived()
+        out = self.engine.input_gradients(input_ids, attention_mask, token_type_ids, gxi, gn, grad, labels=lab)
+        self.engine.check_errors()
+        res = dict(score=out["score"].clone(), grad_x_input=gxi, grad_norm=gn)
+        if return_gradient:
+            res["gradient"] = grad
+        return res
+
     # -------------------------------------------------------------- evaluation / masked prediction (no dense logits)
     def _prep_long(self, t):
         if t is None:
@@ -742,6 +797,43 @@ class STonKGsForSequenceClassification(STonKGsForPreTraining):
         if not return_dict:
             return ((loss,) + (logits,)) if loss is not None else (logits,)
         return SequenceClassifierOutput(loss=loss, logits=logits, hidden_states=None, attentions=None)
+
+    @torch.no_grad()
+    def input_attributions(self, input_ids, attention_mask=None, token_type_ids=None, target=None,
+                           return_gradient: bool = False, max_bytes: int = 1 << 30) -> dict:
+        """Which evidence tokens and which walk entities drive this classification: the gradient of the logit of class
+        ``target`` with respect to the input embeddings (the frozen backbone's output for the text half, the entity
+        table's rows for the other), per position.
+
+        ``target``: None = the predicted class of every sequence (argmax), an int (one class for all), or int64 [B]; a
+        class outside [0, num_labels) raises IndexError. Returns ``logits`` (fp32 [B, num_labels], the eval-mode forward's),
+        ``target`` (int64 [B]), ``grad_x_input`` (fp32 [B, S]: <dF/dx_p, x_p>), ``grad_norm`` (fp32 [B, S]: |dF/dx_p|,
+        saliency) and, with ``return_gradient``, ``gradient`` (fp32 [B, S, H]; allocated up front, refused beyond
+        ``max_bytes``). Padded positions other than position 0 are read by nothing: their entries are exactly 0.
+        Dropout is off in either module mode; see the pre-training class's method for what the call leaves alone."""
+        input_ids, attention_mask, token_type_ids = (self._prep(t) for t in (input_ids, attention_mask, token_type_ids))
+        gxi, gn, grad = self._attribution_buffers(input_ids, return_gradient, max_bytes)
+        B, C = input_ids.shape[0], self.num_labels
+        if target is not None:
+            if torch.is_tensor(target) and target.dim() > 0:
+                if target.dtype in (torch.float16, torch.bfloat16, torch.float32, torch.float64, torch.bool) or \
+                        tuple(target.shape) != (B,):
+                    raise ValueError(f"target must be None, an int, or an integer tensor of shape [{B}]")
+                target = self._prep(target)
+                lo, hi = (int(v) for v in torch.stack([target.min(), target.max()]).tolist()) if B else (0, 0)
+            else:
+                lo = hi = int(target)
+                target = torch.full((B,), lo, dtype=torch.long, device=self._device)
+            if lo < 0 or hi >= C:
+                raise IndexError(f"target class {lo if lo < 0 else hi} is out of range for {C} labels")
+        self._sync_derived()
+        out = self.engine.input_gradients(input_ids, attention_mask, token_type_ids, gxi, gn, grad, num_labels=C,
+                                          target=target)
+        self.engine.check_errors()
+        res = dict(logits=out["logits"].clone(), target=out["target"].clone(), grad_x_input=gxi, grad_norm=gn)
+        if return_gradient:
+            res["gradient"] = grad
+        return res
 
     def forward_backward(self, inputs, gscale: float = 1.0, on_segment_done=None):
         lab, mode = self._labels_and_mode(inputs.get("labels"))
