@@ -332,6 +332,39 @@ int stonk_adamw_step_tiled(float* p, float* g, float* m, float* v, void* p_bf16,
                            int total_tiles, const int64_t* flat_spans_dev, int n_flat, int total_chunks, void* stream);
 int stonk_scale_f32(float* x, int64_t n, float s, void* stream);
 
+/* ---- node2vec (csrc/node2vec.hip): the stage that makes the model's knowledge-graph inputs - the random walks and the
+ * entity table - from an edge list. Replaces ref:src/stonkgs/models/node2vec.py:270-370 (run_node2vec: nodevectors' CPU
+ * walks, gensim's word2vec threads); stonkgs_amd/node2vec.py is the host side. The header comment of the source file
+ * states the random-number formula and both algorithms exactly; tests/test_node2vec_cpu.py restates them in numpy.
+ *
+ * stonk_random_walks: rows [walk_lo, walk_hi) of walks (int32 [W, L], row stride ld) are written, nothing else.
+ * CSR graph: rowptr int64 [N+1], col int32 [nnz], every adjacency list sorted ascending. starts (nullable): int32 [W],
+ * walk w starts at starts[w]; NULL: at w % N; a start outside [0, N) gives a row of -1. thr_*: 24-bit acceptance
+ * thresholds (<= 2^24) of the three classes of a candidate next node - the previous node, a common neighbour of the
+ * previous node, anything else; all equal: a first-order (uniform) walk. Every draw is a pure function of (seed, w, step,
+ * attempt, which): the rows do not depend on how [0, W) is cut into calls. Rejection sampling, at most 32 attempts a step.
+ * Refused before any launch: rowptr / col / walks null (STONK_EINVAL); L < 1, walk_lo < 0, walk_hi < walk_lo, ld < L, N < 1,
+ * a threshold above 2^24 (STONK_ESHAPE); rowptr not 8-byte, col / starts / walks not 4-byte aligned (STONK_EALIGN).
+ * walk_lo == walk_hi returns STONK_OK without a launch. */
+int stonk_random_walks(const int64_t* rowptr, const int32_t* col, int64_t N, const int32_t* starts, int64_t walk_lo,
+                       int64_t walk_hi, int L, uint32_t thr_return, uint32_t thr_common, uint32_t thr_other, uint32_t seed,
+                       int32_t* walks, int64_t ld, void* stream);
+/* stonk_sgns_step: skip-gram with negative sampling over the groups (walk w, position t), w in [walk_lo, walk_hi), t in
+ * [pos_lo, pos_hi), of `walks` (as above). W_in / W_out: fp32 [N, D], contiguous, D % 64 == 0, D <= 1024. Per group: a
+ * reduced window b in [1, window], contexts walk[w][t-b .. t+b] without t, `negatives` noise nodes from the alias table
+ * (alias_thr uint32 [N], alias_idx int32 [N]: a hashed draw picks a slot, slot s is kept iff a second draw < alias_thr[s],
+ * else alias_idx[s]) shared by the group's contexts, a noise node equal to the centre skipped. Mini-batch semantics inside a
+ * group (every gradient scale from the rows as read first), every update a device-scope float atomic add; rows read inside a
+ * launch may be stale with respect to other groups of the same launch - the caller cuts an epoch into many launches and
+ * passes each its own lr. loss_sum_cnt (nullable): [0] += sum of -log sigmoid terms, [1] += their number.
+ * Refused before any launch: walks / W_in / W_out null, an alias array null with negatives > 0 (STONK_EINVAL); D % 64,
+ * D > 1024, window < 1, negatives < 0, L < 1, ld < L, N < 1, an inverted range, positions outside [0, L], 2 * window context
+ * rows of D floats beyond 64 KiB of LDS (STONK_ESHAPE); W_in / W_out not 16-byte, the others not 4-byte aligned
+ * (STONK_EALIGN). An empty range returns STONK_OK without a launch. */
+int stonk_sgns_step(const int32_t* walks, int64_t ld, int L, int64_t walk_lo, int64_t walk_hi, int pos_lo, int pos_hi,
+                    float* W_in, float* W_out, int64_t N, int D, int window, int negatives, const uint32_t* alias_thr,
+                    const int32_t* alias_idx, float lr, uint32_t seed, float* loss_sum_cnt, void* stream);
+
 /* ---- Data-parallel gradient exchange (csrc/comm.hip): RCCL collectives on a stream the LIBRARY owns, handed over by
  * events. Replaces torch DistributedDataParallel's bucketed all-reduce, which the reference gets from HF Trainer when it
  * is launched distributed (ref:src/stonkgs/models/stonkgs_pretraining.py:215-223), and - reduce-scatter / all-gather -

@@ -89,6 +89,10 @@ _SIGNATURES = {
     "stonk_adamw_step_tiled": [_vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _vp, _f32, _f32,
                                _vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _i32, _i32, _vp],
     "stonk_scale_f32": [_vp, _i64, _f32, _vp],
+    # node2vec: random walks and one skip-gram launch (csrc/node2vec.hip)
+    "stonk_random_walks": [_vp, _vp, _i64, _vp, _i64, _i64, _i32, _u32, _u32, _u32, _u32, _vp, _i64, _vp],
+    "stonk_sgns_step": [_vp, _i64, _i32, _i64, _i64, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _f32, _u32,
+                        _vp, _vp],
     # data-parallel gradient exchange: RCCL on a library-owned stream (csrc/comm.hip)
     "stonk_comm_unique_id": [_vp],
     "stonk_comm_init": [C.POINTER(C.c_void_p), _i32, _i32, _vp, _i32],

@@ -204,7 +204,8 @@ class STonKGsForPreTraining(nn.Module):
             g = torch.Generator().manual_seed(seed + 1)
             kg_embeddings = torch.randn(K, cfg.hidden_size, generator=g, dtype=torch.float64) * 0.3
         self._kg_rows = kg_embeddings.to(torch.float32).to(dev)  # fp64 -> fp32 RN, as ref:stonkgs_model.py:193-200
-        numeric_indices = [i for i in range(K + 3) if i not in (SEP_ID, MASK_ID, UNK_ID)]
+        # (a table of fewer than 101 rows ends below the special ids: the reference's zip stops after K indices)
+        numeric_indices = [i for i in range(K + 3) if i not in (SEP_ID, MASK_ID, UNK_ID)][:K]
         names = names if names is not None else [f"node{r}" for r in range(K)] if K <= 4096 else None
         self.kg_idx_to_name = dict(zip(numeric_indices, names)) if names is not None else _LazyNames(numeric_indices)
         self._numeric_indices = torch.tensor(numeric_indices, device=dev)
@@ -238,12 +239,12 @@ class STonKGsForPreTraining(nn.Module):
         eng = self.engine
         eng.refresh_derived(bf16_mirror=True)
         K, H = self.config.kg_vocab_size, self.config.hidden_size
-        table = torch.zeros(K + 3, H, dtype=torch.float32, device=self._device)
+        table = torch.zeros(max(K + 3, MASK_ID + 1), H, dtype=torch.float32, device=self._device)
         table[self._numeric_indices] = self._kg_rows  # TSV row r -> model index numeric_indices[r]  (Q1)
         eng.kg_table = table
         sv = eng.special_vectors()  # (Q2)
         for sid, vec in sv.items():
-            if sid < K + 3:
+            if sid < table.shape[0]:
                 table[sid] = vec
         self.kg_backbone = KGBackbone(table)
         self._mark_synced()
