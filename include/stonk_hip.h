@@ -365,6 +365,40 @@ int stonk_sgns_step(const int32_t* walks, int64_t ld, int L, int64_t walk_lo, in
                     float* W_in, float* W_out, int64_t N, int D, int window, int negatives, const uint32_t* alias_thr,
                     const int32_t* alias_idx, float lr, uint32_t seed, float* loss_sum_cnt, void* stream);
 
+/* ---- Link-prediction score of a node2vec table (csrc/link_prediction.hip): how good a table is, and the figure the
+ * hyper-parameter search maximises. Replaces the device-worthy parts of ref:src/stonkgs/models/node2vec.py:34-71
+ * (run_link_prediction): stellargraph's negative sampling behind EdgeSplitter(kg).train_test_split() (:50), the [n, D]
+ * Hadamard feature matrix (:56-58) and every pass scikit-learn's LogisticRegression.fit / predict makes over it (:66-68).
+ * stonkgs_amd/link_prediction.py is the host side; tests/test_link_prediction_cpu.py restates both kernels in numpy.
+ *
+ * stonk_sample_non_edges: rows [sample_lo, sample_hi) of out (int32 [S, 2]) are written, nothing else. CSR graph as for
+ * stonk_random_walks, symmetric (both directions of every edge present), N nodes. Sample i draws up to 64 ordered pairs
+ * (u, v), uniform over [0, N)^2, and takes the first with u != v and v not adjacent to u; if all 64 are rejected the row is
+ * (-1, -1) and *failures (int32, device; the caller zeroes it) grows by one. Row i is a pure function of (seed, i): it does
+ * not depend on how [0, S) is cut into calls. DUPLICATES ARE ALLOWED: two samples may name the same pair (the reference's
+ * sampler removes duplicates; at the densities this is used at a repeat is rare, and the classifier does not care).
+ * Refused before any launch: rowptr / col / out / failures null (STONK_EINVAL); N < 1, sample_lo < 0, sample_hi < sample_lo,
+ * sample_hi >= 2^30 (STONK_ESHAPE); rowptr not 8-byte, the others not 4-byte aligned (STONK_EALIGN). An empty range returns
+ * STONK_OK without a launch. */
+int stonk_sample_non_edges(const int64_t* rowptr, const int32_t* col, int64_t N, int64_t sample_lo, int64_t sample_hi,
+                           uint32_t seed, int32_t* out, int32_t* failures, void* stream);
+/* stonk_linkpred_lossgrad: one evaluation of the logistic model on Hadamard features, nothing of size [n, D] materialised.
+ * emb fp32 [N, D], row stride ld >= D, D % 64 == 0, 64 <= D <= 1024; pairs int32 [n, 2]; y fp32 [n] (0 or 1); w fp32 [D].
+ * Example e: x = emb[pairs[e][0]] * emb[pairs[e][1]] (elementwise), z = <x, w> + b, loss = softplus(z) - y z,
+ * g = sigmoid(z) - y. Outputs, each skipped when null (at least one is needed): scores fp32 [n] = z; partials fp32
+ * [G, D + 2], G = stonk_linkpred_partial_rows(), row r = workgroup r's [sum g x (D floats), sum g, sum loss] - the caller
+ * sums the G rows (in fp64). Every row of partials is written by every launch. With partials null y may be null too: the
+ * forward pass of decision_function / predict. An example with a node id outside [0, N) contributes nothing and gets the
+ * score NaN. No float atomics; which wavefront adds which example in which order depends on (n, G) alone, and a
+ * workgroup's wavefronts are added in a fixed order: two calls on equal inputs give bit-equal outputs (a line search
+ * compares values of neighbouring points). A sub-range of examples is a call with offset pairs / y / scores pointers.
+ * Refused before any launch: emb / pairs / w null, scores and partials both null, partials without y (STONK_EINVAL);
+ * D % 64, D < 64, D > 1024, ld < D, ld >= 2^31, N < 1, N >= 2^31, n < 0 (STONK_ESHAPE); pairs not 8-byte, the others not
+ * 4-byte aligned (STONK_EALIGN). n == 0 returns STONK_OK without a launch (partials is then left as it is). */
+int64_t stonk_linkpred_partial_rows(void);
+int stonk_linkpred_lossgrad(const float* emb, int64_t ld, int64_t N, int D, const int32_t* pairs, const float* y, int64_t n,
+                            const float* w, float b, float* scores, float* partials, void* stream);
+
 /* ---- Data-parallel gradient exchange (csrc/comm.hip): RCCL collectives on a stream the LIBRARY owns, handed over by
  * events. Replaces torch DistributedDataParallel's bucketed all-reduce, which the reference gets from HF Trainer when it
  * is launched distributed (ref:src/stonkgs/models/stonkgs_pretraining.py:215-223), and - reduce-scatter / all-gather -

@@ -93,6 +93,9 @@ _SIGNATURES = {
     "stonk_random_walks": [_vp, _vp, _i64, _vp, _i64, _i64, _i32, _u32, _u32, _u32, _u32, _vp, _i64, _vp],
     "stonk_sgns_step": [_vp, _i64, _i32, _i64, _i64, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _f32, _u32,
                         _vp, _vp],
+    # link-prediction score of a node2vec table: negatives, one logistic loss / gradient evaluation (csrc/link_prediction.hip)
+    "stonk_sample_non_edges": [_vp, _vp, _i64, _i64, _i64, _u32, _vp, _vp, _vp],
+    "stonk_linkpred_lossgrad": [_vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _f32, _vp, _vp, _vp],
     # data-parallel gradient exchange: RCCL on a library-owned stream (csrc/comm.hip)
     "stonk_comm_unique_id": [_vp],
     "stonk_comm_init": [C.POINTER(C.c_void_p), _i32, _i32, _vp, _i32],
@@ -141,6 +144,8 @@ def lib():
         handle.stonk_layernorm_bwd_workspace_floats.restype = C.c_int64
         handle.stonk_sumsq_workspace_floats.argtypes = []
         handle.stonk_sumsq_workspace_floats.restype = C.c_int64
+        handle.stonk_linkpred_partial_rows.argtypes = []
+        handle.stonk_linkpred_partial_rows.restype = C.c_int64
         handle.stonk_unpad_workspace_ints.argtypes = [_i32]
         handle.stonk_unpad_workspace_ints.restype = C.c_int64
         handle.stonk_comm_stream.argtypes = [_vp]
@@ -151,7 +156,8 @@ def lib():
 
 def exported_symbols():
     return sorted(list(_SIGNATURES) + ["stonk_abi_version", "stonk_layernorm_bwd_workspace_floats",
-                                     "stonk_sumsq_workspace_floats", "stonk_unpad_workspace_ints", "stonk_comm_stream"])
+                                     "stonk_sumsq_workspace_floats", "stonk_unpad_workspace_ints", "stonk_comm_stream",
+                                     "stonk_linkpred_partial_rows"])
 
 
 def check(status: int, name: str) -> None:

@@ -39,20 +39,12 @@
 //     (sc1) load could not promise a fresh row either; staleness ends at the launch boundary, which is why the host cuts an
 //     epoch into many launches (node2vec). Plain loads keep the second read of a target row an L1 hit.
 //   * a node id outside [0, N) in `walks` (the -1 rows above) is skipped: as centre the group, as context the pair.
-#include "common.h"
+#include "n2v_common.h"
 
 #define STONK_WALK_ATTEMPTS 32
 #define STONK_WALK_CHUNK 32
 
 namespace {
-
-__host__ __device__ inline uint32_t n2v_key(uint32_t seedkey, uint32_t w, uint32_t t) {
-  return stonk_hash32(stonk_hash32(seedkey + w) ^ (t * 0x9E3779B1u));
-}
-__host__ __device__ inline uint32_t n2v_draw(uint32_t key, uint32_t attempt, uint32_t which) {
-  return stonk_hash32(key + (2u * attempt + which + 1u) * 0x85EBCA77u);
-}
-__host__ __device__ inline uint32_t n2v_mulhi(uint32_t r, uint32_t n) { return (uint32_t)(((uint64_t)r * n) >> 32); }
 
 __global__ __launch_bounds__(64) void random_walk_kernel(const long* __restrict__ rowptr, const int* __restrict__ col, int N,
                                                          const int* __restrict__ starts, long walk_lo, long walk_hi, int L,
@@ -109,8 +101,6 @@ __global__ __launch_bounds__(64) void random_walk_kernel(const long* __restrict_
     __syncthreads();
   }
 }
-
-__device__ __forceinline__ float softplus(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
 
 // dynamic LDS of a group's wavefront, in floats / ints: context rows, the g(u, j) table, context and target ids
 __host__ __device__ inline long sgns_lds_bytes(int D, int window, int K) {

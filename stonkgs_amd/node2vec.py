@@ -5,14 +5,17 @@ for ``preprocess_df_for_embeddings*``). Replaces ref:src/stonkgs/models/node2vec
 
 Host side only: graph and noise-table construction on the CPU (numpy), device memory and streams through torch, the two
 hot loops in csrc/node2vec.hip (``stonk_random_walks``, ``stonk_sgns_step``). There is no CPU fallback.
+``run_node2vec_hpo`` (ref:node2vec.py:93-257) picks the best of several runs by the link-prediction score of
+stonkgs_amd/link_prediction.py.
 
 Command line: ``python -m stonkgs_amd.node2vec --pretraining_path edges.tsv --embeddings_output_path emb.tsv
---random_walks_output_path walks.tsv``
+--random_walks_output_path walks.tsv`` (one run); with ``--n_trials N`` the search.
 """
 from __future__ import annotations
 
+import itertools
 import os
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
 
 import numpy as np
 
@@ -122,6 +125,8 @@ class Node2Vec:
             self.weights = (float(return_weight), float(neighbor_weight), 1.0)
         self.thresholds = walk_thresholds(*self.weights)
         self.names: Optional[list] = None
+        self.rowptr: Optional[np.ndarray] = None   # the graph of the last fit (link_prediction.py scores the table on it)
+        self.col: Optional[np.ndarray] = None
         self.walks = None
         self.counts: Optional[np.ndarray] = None
         self.loss_history: list = []
@@ -197,6 +202,7 @@ class Node2Vec:
             raise hip.StonkHipError("Node2Vec.fit needs an MI355X: the walk and skip-gram kernels have no CPU fallback")
         src, tgt = _read_edges(edges_or_path, sep)
         self.names, rowptr, col = build_csr(src, tgt)
+        self.rowptr, self.col = rowptr, col
         self._index = {name: i for i, name in enumerate(self.names)}
         n = len(self.names)
         walks = self.random_walks(rowptr, col)
@@ -238,6 +244,74 @@ def run_node2vec(pretraining_path: str, sep: str = "\t", n_threads: Optional[int
     return model
 
 
+HPO_SEARCH_SPACE = {"epochs": [2, 4, 8], "window": [3, 4, 5]}   # ref:node2vec.py:156-158 (window_size: suggest_int(3, 5))
+
+
+def hpo_trials(search_space: dict, n_trials: int, seed: int) -> List[dict]:
+    """The trials of a search: ``min(n_trials, grid size)`` points of the grid ``search_space`` spans (keys in their given
+    order, the last one varying fastest), drawn without replacement by ``np.random.RandomState(seed)``."""
+    keys = list(search_space)
+    grid = list(itertools.product(*(list(search_space[k]) for k in keys)))
+    if not grid or n_trials < 1:
+        raise ValueError("an empty search")
+    picks = np.random.RandomState(seed & 0xFFFFFFFF).choice(len(grid), min(int(n_trials), len(grid)), replace=False)
+    return [dict(zip(keys, grid[i])) for i in picks]
+
+
+def search_trials(trials: List[dict], run_trial, score_key: str = "auc_hard_labels"):
+    """The search loop: ``run_trial(params)`` returns ``(model, report)``; the model whose ``report[score_key]`` is largest
+    is kept (the others are dropped as the loop goes on), ties go to the EARLIER trial. Returns ``(best model,
+    [(params, report), ...])``. Warns when no trial stands out - all scores equal, or a classifier that never left its
+    starting point (``n_iter`` 0: the table's features are too small for the fit's tolerance, typical of a barely
+    trained table) - because the first trial is then returned without having been selected by anything."""
+    import warnings
+
+    best, best_score, results = None, -np.inf, []
+    for params in trials:
+        model, report = run_trial(params)
+        results.append((params, report))
+        if report[score_key] > best_score:
+            best, best_score = model, report[score_key]
+    scores = [r[score_key] for _, r in results]
+    if len(results) > 1 and max(scores) == min(scores):
+        warnings.warn(f"all {len(results)} trials score {scores[0]:.4f}: the first trial is returned, nothing was selected")
+    elif any(r.get("n_iter") == 0 for _, r in results):
+        warnings.warn("a trial's classifier stopped at its starting point (features too small for its tolerance): its score "
+                      "of 0.5 says nothing about the table")
+    return best, results
+
+
+def run_node2vec_hpo(pretraining_path: str, sep: str = "\t", delete_database: bool = True, logging_uri: Optional[str] = None,
+                     n_trials: int = 1, n_threads: Optional[int] = None, seed: Optional[int] = None, *,
+                     embeddings_output_path: str, random_walks_output_path: str, search_space: Optional[dict] = None,
+                     **fixed):
+    """ref:node2vec.py:93-257: several node2vec runs over ``epochs`` in {2, 4, 8} and ``window`` in {3, 4, 5}, everything
+    else as in ``run_node2vec`` (or ``fixed``), each scored by ``link_prediction_report``; the best one's two TSV files
+    are written. There is no optuna here: the trials are ``hpo_trials(search_space, n_trials, seed)``, grid points without
+    replacement. The positive and negative pairs are drawn ONCE and shared by all trials, so the scores are comparable
+    (the reference redraws them per trial). The score is the reference's figure, ``auc_hard_labels``; ties go to the
+    earlier trial. ``delete_database``, ``logging_uri`` and ``n_threads`` are accepted and ignored (no study database, no
+    mlflow, no CPU threads). Returns ``(best model, [(params, report), ...])``."""
+    from .link_prediction import link_prediction_examples, link_prediction_report
+
+    if seed is None:
+        seed = int(np.random.randint(1, 2 ** 31 - 1))
+    trials = hpo_trials(search_space or HPO_SEARCH_SPACE, n_trials, seed)
+    src, tgt = _read_edges(pretraining_path, sep)
+    edges = list(zip(src, tgt))
+    _, rowptr, col = build_csr(src, tgt)
+    examples = link_prediction_examples(rowptr, col, seed=seed)
+
+    def run_trial(params):
+        model = Node2Vec(**{"seed": seed & 0xFFFFFFFF, **fixed, **params}).fit(edges)
+        return model, link_prediction_report(model, seed=seed, examples=examples)
+
+    best, results = search_trials(trials, run_trial)
+    best.save_embeddings(embeddings_output_path)
+    best.save_walks(random_walks_output_path)
+    return best, results
+
+
 def main(argv=None) -> None:
     import argparse
 
@@ -248,7 +322,16 @@ def main(argv=None) -> None:
     ap.add_argument("--embeddings_output_path", required=True)
     ap.add_argument("--random_walks_output_path", required=True)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--n_trials", type=int, default=None, help="run the hyper-parameter search with this many trials")
     a = ap.parse_args(argv)
+    if a.n_trials is not None:
+        m, results = run_node2vec_hpo(a.pretraining_path, a.sep, n_trials=a.n_trials, n_threads=a.n_threads, seed=a.seed,
+                                      embeddings_output_path=a.embeddings_output_path,
+                                      random_walks_output_path=a.random_walks_output_path)
+        for params, report in results:
+            print(f"{params}: score {report['auc_hard_labels']:.4f}  auc {report['auc']:.4f}")
+        print(f"best: epochs {m.epochs}, window {m.window}; {len(m.names)} nodes")
+        return
     m = run_node2vec(a.pretraining_path, a.sep, a.n_threads, embeddings_output_path=a.embeddings_output_path,
                      random_walks_output_path=a.random_walks_output_path, seed=a.seed)
     print(f"{len(m.names)} nodes, mean loss per epoch {m.loss_history}")
