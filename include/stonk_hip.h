@@ -399,6 +399,58 @@ int64_t stonk_linkpred_partial_rows(void);
 int stonk_linkpred_lossgrad(const float* emb, int64_t ld, int64_t N, int D, const int32_t* pairs, const float* y, int64_t n,
                             const float* w, float b, float* scores, float* partials, void* stream);
 
+/* ---- KG baseline (csrc/kg_baseline.hip): the knowledge-graph-only classifier every STonKGs fine-tuning result is
+ * compared against, ref:src/stonkgs/models/kg_baseline_model.py. Replaces the [n, L, D] float64 host array of its datasets
+ * (:186, :249) by one gather-and-max pass, and its lightning training loop (batch 8, 100 epochs: 10^6 optimizer steps per
+ * fold) by a kernel that walks many steps with the model on chip, all folds side by side. stonkgs_amd/kg_baseline_model.py
+ * is the host side; tests/test_kg_baseline_cpu.py restates the dropout rule and the step.
+ *
+ * stonk_walk_maxpool: pooled[e, d] = max_t table[ids[e, t], d]. ids int32 [n, L], row stride ld_ids >= L, L >= 1; table fp32
+ * [N, D], row stride ld_table; pooled fp32 [n, D], row stride ld_pooled; D % 64 == 0, 64 <= D <= 1024. Id -1 is the
+ * reference's null vector (:155): a row of zeros that takes part in the maximum. Any other id outside [0, N) makes that
+ * example's row NaN and adds one (per example) to *errors (int32, device; the caller zeroes it). The maximum is exact: for a
+ * finite table the result is bit-identical to torch.max(x, dim=1).values. A NaN in the table is NOT propagated as torch
+ * does (the hardware maximum drops a NaN operand). A sub-range of examples is a call with offset ids / pooled pointers.
+ * Refused before any launch: a null pointer (STONK_EINVAL); D, L, the strides, N < 1 or >= 2^31, n < 0 or >= 2^31
+ * (STONK_ESHAPE); table / pooled not 16-byte aligned, ld_table % 4, ld_pooled % 4, ids / errors not 4-byte aligned
+ * (STONK_EALIGN). n == 0 returns STONK_OK without a launch. */
+int stonk_walk_maxpool(const int32_t* ids, int64_t ld_ids, int64_t n, int L, const float* table, int64_t ld_table, int64_t N,
+                       int D, float* pooled, int64_t ld_pooled, int32_t* errors, void* stream);
+/* stonk_kgb_train_steps: R independent runs (cross-validation folds), one workgroup each, every run walking its own span of
+ * consecutive optimizer steps of  dropout(p) -> linear [C, D] -> softmax -> CrossEntropyLoss(weight, "mean") ON THE
+ * PROBABILITIES (the reference's quirk, :93-110: a second log-softmax is taken over the softmax output; the gradient goes
+ * back through both) -> torch.optim.AdamW (decoupled weight decay, bias corrections by the global step number, no clipping,
+ * no schedule).
+ * PER-RUN LAYOUT, run r = 0 .. R - 1, all on the device: order int32, row r at order + r * ld_order, `batch` example indices
+ * per step, -1 pads a ragged batch; n_steps int32 [R]; first_step int32 [R], the global index of the span's first step (the
+ * step that uses Adam's t = 1 has index 0); class_weights fp32 [R, C]; W, mW, vW fp32 [R, C, D]; b, mb, vb fp32 [R, C]; loss
+ * fp32, row r at loss + r * ld_loss, one value per step of the span; errors int32 [R]. Shared: pooled fp32 [n, D] with row
+ * stride ld_pooled, labels int32 [n], the scalars (AdamW's are fp64, as torch keeps them: 1 - beta taken from an fp32 beta
+ * would be off by 1e-5 of itself). Run r executes min(n_steps[r], n_steps_max) steps; n_steps_max (host) is
+ * what the launcher checks against the cap stonk_kgb_max_steps() and against ld_order / ld_loss.
+ * W, b and the moments are read at the start of the launch, stay in registers / LDS between the steps and are written back
+ * at its end. The dropout keep decision is a pure function of (seed, run, global step, row in batch, feature) and the bias
+ * corrections of the global step, so cutting a span into several launches changes no bit. Every reduction has a fixed
+ * order, there are no float atomics: equal inputs give equal bits. The only synchronisation is the workgroup barrier.
+ * An order entry outside [-1, n) or a label outside [0, C): the row contributes nothing (as if padded) and errors[r] is set
+ * to 1 (the caller zeroes it). A step without a single valid row reports the loss 0 / 0 and updates nothing.
+ * Refused before any launch, there is no fallback: a null pointer, p outside [0, 1), a beta outside [0, 1), lr < 0
+ * (STONK_EINVAL); C outside [2, 16], batch outside [1, 64], D % 64, D outside [64, 1024], n_steps_max above the cap,
+ * ld_order < n_steps_max * batch, ld_loss < n_steps_max, ld_pooled < D, n < 1 (STONK_ESHAPE); a pointer not 4-byte aligned
+ * (STONK_EALIGN). R == 0 or n_steps_max == 0 returns STONK_OK without a launch. */
+int64_t stonk_kgb_max_steps(void);
+int stonk_kgb_train_steps(const float* pooled, int64_t ld_pooled, int64_t n, int D, const int32_t* labels, int C, int R,
+                          const int32_t* order, int64_t ld_order, int batch, const int32_t* n_steps, const int32_t* first_step,
+                          int n_steps_max, const float* class_weights, float* W, float* b, float* mW, float* vW, float* mb,
+                          float* vb, float* loss, int64_t ld_loss, int32_t* errors, double lr, double beta1, double beta2,
+                          double eps, double weight_decay, float p, uint32_t seed, void* stream);
+/* stonk_kgb_predict: eval mode (no dropout). Example j = idx[j] (int32 [k], indices into pooled): probs fp32 [k, C] =
+ * softmax(pooled[idx[j]] W^T + b), pred int32 [k] = the arg-max of the probabilities, the LOWEST index on a tie (what
+ * torch.argmax returns for a first maximum). An index outside [0, n): the row of probs is NaN, pred -1, *errors grows by one.
+ * Refusals as for stonk_kgb_train_steps; k == 0 returns STONK_OK without a launch. */
+int stonk_kgb_predict(const float* pooled, int64_t ld_pooled, int64_t n, int D, const int32_t* idx, int64_t k, const float* W,
+                      const float* b, int C, float* probs, int32_t* pred, int32_t* errors, void* stream);
+
 /* ---- Data-parallel gradient exchange (csrc/comm.hip): RCCL collectives on a stream the LIBRARY owns, handed over by
  * events. Replaces torch DistributedDataParallel's bucketed all-reduce, which the reference gets from HF Trainer when it
  * is launched distributed (ref:src/stonkgs/models/stonkgs_pretraining.py:215-223), and - reduce-scatter / all-gather -

@@ -35,7 +35,7 @@ LOSS_MSE, LOSS_MSE_BROADCAST, LOSS_BCE = 0, 1, 2
 OK, EINVAL, ESHAPE, EALIGN = 0, -1, -2, -3   # launcher status codes (include/stonk_hip.h)
 ATTN_BWD_DELTA, ATTN_BWD_DQ, ATTN_BWD_DKV, ATTN_BWD_ALL = 1, 2, 4, 7
 
-_vp, _i32, _i64, _f32, _u32 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint32
+_vp, _i32, _i64, _f32, _u32, _f64 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint32, C.c_double
 
 # name -> argtypes; every launcher returns int (0 ok, <0 bad argument, >0 hipError_t)
 _SIGNATURES = {
@@ -96,6 +96,11 @@ _SIGNATURES = {
     # link-prediction score of a node2vec table: negatives, one logistic loss / gradient evaluation (csrc/link_prediction.hip)
     "stonk_sample_non_edges": [_vp, _vp, _i64, _i64, _i64, _u32, _vp, _vp, _vp],
     "stonk_linkpred_lossgrad": [_vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _f32, _vp, _vp, _vp],
+    # KG baseline: pooled walk embeddings, the on-chip training loop of the linear classifier, prediction (csrc/kg_baseline.hip)
+    "stonk_walk_maxpool": [_vp, _i64, _i64, _i32, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp],
+    "stonk_kgb_train_steps": [_vp, _i64, _i64, _i32, _vp, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp,
+                              _vp, _vp, _vp, _i64, _vp, _f64, _f64, _f64, _f64, _f64, _f32, _u32, _vp],
+    "stonk_kgb_predict": [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp],
     # data-parallel gradient exchange: RCCL on a library-owned stream (csrc/comm.hip)
     "stonk_comm_unique_id": [_vp],
     "stonk_comm_init": [C.POINTER(C.c_void_p), _i32, _i32, _vp, _i32],
@@ -146,6 +151,8 @@ def lib():
         handle.stonk_sumsq_workspace_floats.restype = C.c_int64
         handle.stonk_linkpred_partial_rows.argtypes = []
         handle.stonk_linkpred_partial_rows.restype = C.c_int64
+        handle.stonk_kgb_max_steps.argtypes = []
+        handle.stonk_kgb_max_steps.restype = C.c_int64
         handle.stonk_unpad_workspace_ints.argtypes = [_i32]
         handle.stonk_unpad_workspace_ints.restype = C.c_int64
         handle.stonk_comm_stream.argtypes = [_vp]
@@ -157,7 +164,7 @@ def lib():
 def exported_symbols():
     return sorted(list(_SIGNATURES) + ["stonk_abi_version", "stonk_layernorm_bwd_workspace_floats",
                                      "stonk_sumsq_workspace_floats", "stonk_unpad_workspace_ints", "stonk_comm_stream",
-                                     "stonk_linkpred_partial_rows"])
+                                     "stonk_linkpred_partial_rows", "stonk_kgb_max_steps"])
 
 
 def check(status: int, name: str) -> None:
