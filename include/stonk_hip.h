@@ -451,6 +451,47 @@ int stonk_kgb_train_steps(const float* pooled, int64_t ld_pooled, int64_t n, int
 int stonk_kgb_predict(const float* pooled, int64_t ld_pooled, int64_t n, int D, const int32_t* idx, int64_t k, const float* W,
                       const float* b, int C, float* probs, int32_t* pred, int32_t* errors, void* stream);
 
+/* ---- TransE (csrc/transe.hip): trains and ranks the table that ref:src/stonkgs/constants.py:70 names
+ * transe_embeddings_best_model.tsv and ref:src/stonkgs/models/kg_baseline_model.py:208-267 reads (the reference does not
+ * produce it; its authors used PyKEEN outside the package). stonkgs_amd/transe.py is the host side; the source file's
+ * header states the algorithm and the random-number formula, tests/test_transe_cpu.py restates both in numpy.
+ * Shared: ent fp32 [N_e, D], rel fp32 [N_r, D], contiguous, 16-byte aligned; D % 64 == 0, 64 <= D <= 1024; norm 1 or 2.
+ *
+ * stonk_transe_step: one slice of a margin-ranking pass with plain SGD, one wavefront per group g in [g_lo, g_hi). The
+ * group's triple is triples[order ? order[g] : g] (triples int32 [n, 3] of (head, relation, tail); order nullable int32
+ * [n]); `negatives` corrupted triples per group - each replaces the head or the tail by a uniform entity, a replacement
+ * equal to what it replaces is skipped - drawn as pure functions of (seed, g, epoch, j). Loss: sum over the terms of
+ * max(0, margin + ||h + r - t|| - ||h' + r - t'||), the norm itself for norm 2. Mini-batch semantics inside a group, one
+ * device-scope float atomic add of -lr * grad per destination row; rows read inside a launch may be stale with respect to
+ * other groups of the same launch - the caller cuts an epoch into many launches. A triple with an id outside its table (or
+ * an order entry outside [0, n)) is skipped. loss_sum_cnt (nullable float [2]): [0] += the loss, [1] += the number of
+ * non-skipped terms.
+ * Refused before any launch: ent / rel / triples null, norm not 1 or 2 (STONK_EINVAL); D off the rule, negatives < 1,
+ * negatives * (D + 1) floats beyond 64 KiB of LDS, N_e or N_r < 1, N_e / N_r / n >= 2^31, g_lo < 0, g_hi < g_lo, g_hi > n
+ * (STONK_ESHAPE); ent / rel not 16-byte, the others not 4-byte aligned (STONK_EALIGN). g_lo == g_hi returns STONK_OK
+ * without a launch. */
+int stonk_transe_step(float* ent, float* rel, int64_t N_e, int64_t N_r, int D, const int32_t* triples, int64_t n,
+                      const int32_t* order, int64_t g_lo, int64_t g_hi, int negatives, int norm, float margin, float lr,
+                      uint32_t seed, uint32_t epoch, float* loss_sum_cnt, void* stream);
+/* stonk_rows_l2_normalize: rows [row_lo, row_hi) of table (fp32, row stride ld >= D floats) become row / ||row||_2; a row
+ * with norm < 1e-12 is left as it is; nothing outside the range is written.
+ * Refused: table null (STONK_EINVAL); D off the rule, ld < D, ld >= 2^31, row_lo < 0, row_hi < row_lo, row_hi >= 2^31
+ * (STONK_ESHAPE); table not 16-byte aligned (STONK_EALIGN). An empty range returns STONK_OK without a launch. */
+int stonk_rows_l2_normalize(float* table, int64_t ld, int64_t row_lo, int64_t row_hi, int D, void* stream);
+/* stonk_transe_rank: queries int32 [Q, 3]; side 0 ranks the tail (v = h + r, true entity t), side 1 the head (v = t - r,
+ * true entity h). dist(c) = ||v - ent[c]||_1 (norm 1) or the SQUARED L2 distance (norm 2). less / equal (int32 [Q]): the
+ * number of candidates with dist < / == the true entity's; every distance, the true one's included, goes through one
+ * instruction sequence, so equal >= 1 when the true entity is a candidate. Candidates: all of [0, N_e) when cand_ptr is
+ * null, else cand[cand_ptr[q] .. cand_ptr[q+1]) (cand_ptr int64 [Q+1], cand int32 [n_cand]; a range is clipped to
+ * [0, n_cand], an id outside [0, N_e) is ignored). A query with an id out of range gets less = equal = -1. No [Q, N_e]
+ * matrix exists: a workgroup keeps 16 query vectors in LDS and reads each entity row once per 16 queries.
+ * Refused: ent / rel / queries / less / equal null, cand null with cand_ptr given and n_cand > 0, norm not 1 or 2, side not
+ * 0 or 1 (STONK_EINVAL); D off the rule, N_e or N_r < 1 or >= 2^31, Q < 0 or >= 2^31, n_cand < 0 (STONK_ESHAPE); ent / rel
+ * not 16-byte, cand_ptr not 8-byte, the others not 4-byte aligned (STONK_EALIGN). Q == 0 returns STONK_OK without a launch. */
+int stonk_transe_rank(const float* ent, const float* rel, int64_t N_e, int64_t N_r, int D, int norm, const int32_t* queries,
+                      int64_t Q, int side, const int64_t* cand_ptr, const int32_t* cand, int64_t n_cand, int32_t* less,
+                      int32_t* equal, void* stream);
+
 /* ---- Data-parallel gradient exchange (csrc/comm.hip): RCCL collectives on a stream the LIBRARY owns, handed over by
  * events. Replaces torch DistributedDataParallel's bucketed all-reduce, which the reference gets from HF Trainer when it
  * is launched distributed (ref:src/stonkgs/models/stonkgs_pretraining.py:215-223), and - reduce-scatter / all-gather -

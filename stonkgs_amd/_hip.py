@@ -101,6 +101,10 @@ _SIGNATURES = {
     "stonk_kgb_train_steps": [_vp, _i64, _i64, _i32, _vp, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp,
                               _vp, _vp, _vp, _i64, _vp, _f64, _f64, _f64, _f64, _f64, _f32, _u32, _vp],
     "stonk_kgb_predict": [_vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp],
+    # TransE: one margin-ranking SGD launch, the entity constraint, rank evaluation (csrc/transe.hip)
+    "stonk_transe_step": [_vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _f32, _f32, _u32, _u32, _vp, _vp],
+    "stonk_rows_l2_normalize": [_vp, _i64, _i64, _i64, _i32, _vp],
+    "stonk_transe_rank": [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _vp],
     # data-parallel gradient exchange: RCCL on a library-owned stream (csrc/comm.hip)
     "stonk_comm_unique_id": [_vp],
     "stonk_comm_init": [C.POINTER(C.c_void_p), _i32, _i32, _vp, _i32],
