@@ -113,6 +113,21 @@ int stonk_text_embed_ln_fwd(const int64_t* input_ids, int64_t ld_ids, const floa
 int stonk_embed_grad(const void* dx, const int64_t* token_type_ids, float* dpos, float* dtype, int B, int S, int H,
                      int type_rows, const int* row_of_pos, void* stream);
 
+/* Gradient of a TRAINABLE word-embedding lookup (csrc/text_embed.hip): the text-only BERT of
+ * ref:src/stonkgs/models/nlp_baseline_model.py:171-173 trains `bert.embeddings.word_embeddings.weight`, which STonKGs
+ * leaves dead. Replaces the backward of nn.Embedding(V, H, padding_idx) in BertEmbeddings, hf:models/bert/modeling_bert.py:98-108
+ * (torch's embedding_dense_backward). dsum: bf16 [rows, H] with row stride ld - the input gradient of the embeddings LayerNorm
+ * (what the backward of stonk_joint_embed_ln_fwd produces). For padded position p = b*S + s: r = row_of_pos ? row_of_pos[p] : p
+ * (row_of_pos nullable: the packed layout of stonk_unpad_plan); r < 0 (dropped) and input_ids[p] == padding_idx (-1 = no padding
+ * row) contribute nothing; an id outside [0, vocab) sets bit 0 of *err_flag and touches no memory; otherwise
+ * dword[id, :] += float(dsum[r, :]) (fp32 [vocab, H] with row stride ld_w). ACCUMULATES (gradient accumulation; the optimizer
+ * zeroes the buffer). One wavefront per position, 16-byte loads, no-return fp32 atomics of 256 contiguous bytes per
+ * wave-instruction: the sum's last bits depend on the arrival order. Refused before any launch: dsum / input_ids / dword /
+ * err_flag null (STONK_EINVAL); H % 8, H > 4096, ld < H, ld_w < H, vocab <= 0, padding_idx >= vocab, S <= 0, B * S >= 2^31
+ * (STONK_ESHAPE); dsum not 16-byte aligned, ld % 8, dword not 4-byte aligned (STONK_EALIGN). B == 0 returns STONK_OK. */
+int stonk_word_embed_grad(const void* dsum, int64_t ld, const int64_t* input_ids, const int* row_of_pos, float* dword,
+                          int64_t ld_w, int64_t vocab, int padding_idx, int B, int S, int H, int* err_flag, void* stream);
+
 /* Input attributions from d F / d(embedding sum) (csrc/input_attribution.hip). The reference has no call for this: the
  * nearest is autograd with respect to the `inputs_embeds` of ref:src/stonkgs/models/stonkgs_model.py:193-210, which a
  * reference user reaches only by patching `forward` (the tensor is built inside it from ids). dsum: bf16 [rows, H] with row

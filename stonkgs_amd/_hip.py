@@ -53,6 +53,7 @@ _SIGNATURES = {
     "stonk_text_embed_ln_fwd": [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _f32, _i32, _f32,
                                 _u32, _vp, _vp],
     "stonk_embed_grad": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp],
+    "stonk_word_embed_grad": [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp],
     "stonk_input_attribution": [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _f32, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp],
     "stonk_attention_fwd": [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _f32, _f32, _u32, _vp],
     "stonk_attention_bwd": [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i32,

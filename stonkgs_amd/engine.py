@@ -705,6 +705,29 @@ class Engine:
         return dict(row_of_pos=row_of_pos, pos_of_row=pos_of_row, cu=cu, row_mask=row_mask, read_rows=read_rows,
                     read_of_pos=read_of_pos, cu_rd=cu_rd), ev
 
+    @property
+    def half_length(self) -> int:
+        """Positions of a sequence the embeddings kernel takes from `_text_half`'s rows; the rest are table lookups."""
+        return self.cfg.half_length
+
+    def _text_half(self, input_ids, B, training: bool):
+        """F1 frozen backbone (no attention mask: quirk Q5; always padded - its padding positions ARE attended). Returns
+        (text_hidden, hint): `hint` = the next batch's ids when their prefetch is still to be queued by the caller."""
+        S, half = self.cfg.max_position_embeddings, self.half_length
+        with self.block("K1 frozen backbone fwd"):
+            text_hidden = self._take_prefetched(input_ids, training)
+            hit = text_hidden is not None
+            if not hit:
+                text_hidden = self.backbone_fwd(input_ids, S, B, half, training)
+            # The next batch's backbone forward, if the trainer named the batch. After a hit it is queued HERE, before the
+            # wait for the optimizer: it then runs beside AdamW (HBM-bound) and the encoder forward below. After a miss the
+            # inline forward's scratch buffers are still to be read by the embedding kernel: queued behind that kernel.
+            hint, self.next_input_ids = self.next_input_ids, None
+            if hint is not None and hit:
+                self.prefetch_backbone(hint, training)
+                hint = None
+        return text_hidden, hint
+
     def encode(self, input_ids, attention_mask, token_type_ids, training: bool, save: dict, unpad_labels=None,
                layout: Optional[dict] = None, attn_maps: Optional[dict] = None):
         """F1-F4: frozen backbone, KG gather + embeddings LayerNorm, encoder layers, pooler. Shared by the pre-training
@@ -716,7 +739,7 @@ class Engine:
         `attn_maps` (forward-only, padded layout, dropout off): {layer index: (probs or None, modal_mass or None)} - the
         selected layers write their attention probabilities into these tensors (`layer_fwd`)."""
         cfg = self.cfg
-        H, S, half = cfg.hidden_size, cfg.max_position_embeddings, cfg.half_length
+        H, S, half = cfg.hidden_size, cfg.max_position_embeddings, self.half_length
         B = input_ids.shape[0]
         cap = B * S
         if attn_maps and (training or save is not None or unpad_labels is not None):
@@ -730,19 +753,7 @@ class Engine:
         plan = ev = None
         if unpad_labels is not None and attention_mask is not None and self.unpad and B > 0:
             plan, ev = self._plan_rows(attention_mask, unpad_labels[0], unpad_labels[1], B, S, half, keep=save is not None)
-        # F1 frozen backbone (no attention mask: quirk Q5; always padded - its padding positions ARE attended)
-        with self.block("K1 frozen backbone fwd"):
-            text_hidden = self._take_prefetched(input_ids, training)
-            hit = text_hidden is not None
-            if not hit:
-                text_hidden = self.backbone_fwd(input_ids, S, B, half, training)
-            # The next batch's backbone forward, if the trainer named the batch. After a hit it is queued HERE, before the
-            # wait for the optimizer: it then runs beside AdamW (HBM-bound) and the encoder forward below. After a miss the
-            # inline forward's scratch buffers are still to be read by the embedding kernel: queued behind that kernel.
-            hint, self.next_input_ids = self.next_input_ids, None
-            if hint is not None and hit:
-                self.prefetch_backbone(hint, training)
-                hint = None
+        text_hidden, hint = self._text_half(input_ids, B, training)
         self.wait_params()   # everything above read frozen weights only; from here on the trainable ones
         T, rows, cu, mask, rd = cap, cap, None, attention_mask, None
         if plan is not None:
@@ -807,7 +818,7 @@ class Engine:
         hip.call("stonk_small_linear_fwd", first.data_ptr(), ld_first, f("bert.pooler.dense.weight").data_ptr(),
                  f("bert.pooler.dense.bias").data_ptr(), pooled.data_ptr(), B, H, H, hip.SMALL_TANH, st)
         if save is not None:   # (None: forward-only callers - embedding extraction, batched inference)
-            save.update(B=B, attention_mask=mask, token_type_ids=token_type_ids, sum0=sum0, st0=st0,
+            save.update(B=B, input_ids=input_ids, attention_mask=mask, token_type_ids=token_type_ids, sum0=sum0, st0=st0,
                         seq_out=seq_out, pooled=pooled, p_hid=p_hid, p_att=p_att, T=T, rows=rows, plan=plan,
                         first=first, ld_first=ld_first, rd=rd, Th=Th, first_rows=first_rows, text_hidden=text_hidden,
                         head_map=None if plan is None else (plan["row_of_pos"] if rd is None else plan["read_of_pos"]))
@@ -1310,10 +1321,15 @@ class Engine:
                      g_("bert.embeddings.position_embeddings.weight").data_ptr(),
                      g_("bert.embeddings.token_type_embeddings.weight").data_ptr(), B, S, H, cfg.type_vocab_size,
                      0 if plan is None else plan["row_of_pos"].data_ptr(), st)
+            self._word_embed_grad(dsum, sv)
         notify("bert.embeddings")
         self.mark("backward_end")
         self.join_wgrad()
         return dsum
+
+    def _word_embed_grad(self, dsum, sv) -> None:
+        """Gradient of the looked-up input rows, where they are trainable (`TextEngine`); STonKGs' entity table and its
+        frozen backbone are not."""
 
     # ------------------------------------------------------------------ sequence classification head (config 5)
     def forward_cls(self, input_ids, attention_mask, token_type_ids, labels, num_labels: int, training: bool,
@@ -1381,3 +1397,53 @@ class Engine:
         dseq = self.buf("b.dseq", (B * S, H))
         dseq[:sv["Th"]].zero_()  # only position 0 of every sequence receives a gradient (from the pooler)
         self.backward_encoder(dpooled, dseq, sv, notify)
+
+
+TEXT_ERR_BITS = {1: "token id outside [0, vocab_size)", 2: ERR_BITS[2], 16: "class label outside [0, num_labels)"}
+
+
+class TextEngine(Engine):
+    """Text-only front and tail for a plain BERT classifier (the NLP baseline, ref:src/stonkgs/models/nlp_baseline_model.py):
+    the input is token ids alone. No frozen backbone, no entity table, no special vectors - every position's input row is a
+    lookup in the TRAINABLE word table `bert.embeddings.word_embeddings.weight`, which stonk_joint_embed_ln_fwd reads as its
+    table with half = 0 (word + position + token-type -> LayerNorm -> dropout, packed layout included) and whose gradient
+    stonk_word_embed_grad adds behind stonk_embed_grad, before the "bert.embeddings" notification: the table is the last
+    segment of the flat buffer. Encoder layers, pooler, `forward_cls` / `backward_cls` and the optimizer tables are the
+    base class's. Only the gather reads the table: it has no W^T copy, and its bf16 mirror is never read."""
+
+    WORD = "bert.embeddings.word_embeddings.weight"
+    PADDING_IDX = 0   # BertEmbeddings: nn.Embedding(vocab_size, hidden_size, padding_idx=config.pad_token_id = 0)
+
+    def __init__(self, cfg: STonKGsConfig, store: FlatStore, device):
+        super().__init__(cfg, store, None, 0, device)
+        self.kg_table = store.view(self.WORD)   # fp32 [vocab, H]: a view of the master, so it is always current
+
+    @property
+    def half_length(self) -> int:
+        return 0
+
+    def _text_half(self, input_ids, B, training: bool):
+        """Nothing runs ahead of the embeddings kernel; with half = 0 it reads no text row (the pointer must be non-null)."""
+        self.next_input_ids = None
+        return self.kg_table, None
+
+    def refresh_derived(self, bf16_mirror: bool = True) -> None:
+        st = hip.stream_ptr()
+        if bf16_mirror:
+            hip.call("stonk_cast_f32_to_bf16", self.P.data.data_ptr(), self.P.bf16.data_ptr(), self.P.numel, st)
+        self._refresh_wt(st)
+
+    def _word_embed_grad(self, dsum, sv) -> None:
+        cfg, plan = self.cfg, sv["plan"]
+        dword = self.P.grad_view(self.WORD)
+        hip.call("stonk_word_embed_grad", dsum.data_ptr(), dsum.stride(0), sv["input_ids"].data_ptr(),
+                 0 if plan is None else plan["row_of_pos"].data_ptr(), dword.data_ptr(), dword.stride(0), cfg.vocab_size,
+                 self.PADDING_IDX, sv["B"], cfg.max_position_embeddings, cfg.hidden_size, self.err.data_ptr(),
+                 hip.stream_ptr())
+
+    def check_errors(self) -> None:
+        """As the base class, but an out-of-range token id is an IndexError: what torch's embedding raises."""
+        e = int(self.err.item())
+        if e:
+            self.err.zero_()
+            raise IndexError("; ".join(TEXT_ERR_BITS.get(b, m) for b, m in ERR_BITS.items() if e & b))
