@@ -65,6 +65,19 @@ int stonk_gemm_tn_bf16(const void* dY, int64_t lda, const void* X, int64_t ldb, 
  * a bias only when N' <= 256 (that kernel shares the bias sums out over its column tiles), else STONK_ESHAPE. */
 int stonk_gemm_tn_bf16_store(const void* dY, int64_t lda, const void* X, int64_t ldb, float* dW, int64_t ldc, float* dbias,
                              int M, int N, int K, float alpha, int split_k, const int* k_dev, void* stream);
+/* stonk_gemm_tn_bf16_store (same routing, same refusals) that also leaves, for every output tile of the kernel it routes
+ * to - 256x256 with split_k <= 0, else 128x128 - the sum of the squares of the values it stored (after the multiplication
+ * by alpha; rows >= M' and columns >= N' of an edge tile are not stored and not counted):
+ * tile_sumsq[row_tile * col_tiles + col_tile]. Every slot is written by every launch, zeros when *k_dev leaves no K tile: the
+ * caller zeroes nothing. The order of summation inside a tile is fixed, so a slot depends on the inputs alone - not on the
+ * grid, not on the launch. n_slots < the tile count: STONK_EINVAL. A gradient-norm pass takes the slots as the `extra` of
+ * stonk_sumsq_f32_plus instead of reading dW back.
+ * stonk_gemm_tn_store_tiles: that tile count for a shape and split_k, or the (negative) status with which the store entry
+ * refuses the shape; nothing is launched. */
+int stonk_gemm_tn_bf16_store_sumsq(const void* dY, int64_t lda, const void* X, int64_t ldb, float* dW, int64_t ldc,
+                                   float* dbias, int M, int N, int K, float alpha, int split_k, const int* k_dev,
+                                   float* tile_sumsq, int64_t n_slots, void* stream);
+int64_t stonk_gemm_tn_store_tiles(int M, int N, int K, int split_k);
 
 /* y = dropout(LayerNorm(x)); x,y bf16 [rows,H]; gamma/beta fp32; mean/rstd fp32 [rows] saved for backward.
  * Replaces nn.LayerNorm(eps=1e-12) + nn.Dropout at hf:modeling_bert.py:106-107, :291-292, :349-350, :479. */
@@ -319,6 +332,13 @@ int stonk_gelu_bwd_bf16(const void* dg, const void* u, void* du, int64_t n, void
  * fused clip_grad_norm_(max_grad_norm) + AdamW + bf16 weight refresh + grad zeroing. */
 int64_t stonk_sumsq_workspace_floats(void);
 int stonk_sumsq_f32(const float* x, int64_t n, float* out_accum, float* workspace, int64_t ws_floats, void* stream);
+/* stonk_sumsq_f32 that also adds n_extra ready-made sums (device floats; nullable with n_extra == 0): the block that
+ * finishes last adds them to its total in index order, behind the partial sums of x - one fixed order, no launch of its
+ * own: 64 consecutive runs of ceil(n_extra / 64) extras are each summed element by element and the run sums are added to
+ * the total one after the other, all in fp64, rounded to fp32 once at the end. Without extras: stonk_sumsq_f32, bit for
+ * bit. */
+int stonk_sumsq_f32_plus(const float* x, int64_t n, float* out_accum, float* workspace, int64_t ws_floats,
+                         const float* extra, int64_t n_extra, void* stream);
 /* stonk_adamw_step works on any piece of the flat buffers (pointers into p / g / p_bf16 at the piece, m / v wherever the
  * caller keeps that piece's state: an optimizer sharded over data-parallel ranks updates its 1/world of every gradient
  * bucket). decay_spans (nullable, device): n_spans sorted [lo, hi) element ranges of the WHOLE flat buffer that receive

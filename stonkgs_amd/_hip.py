@@ -43,6 +43,7 @@ _SIGNATURES = {
                            _f32, _i32, _vp, _vp, _f32, _u32, _i32, _vp],
     "stonk_gemm_tn_bf16": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _f32, _i32, _vp, _vp],
     "stonk_gemm_tn_bf16_store": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _f32, _i32, _vp, _vp],
+    "stonk_gemm_tn_bf16_store_sumsq": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _i64, _vp],
     "stonk_layernorm_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _i32, _f32, _u32, _vp],
     "stonk_layernorm_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _u32, _f32, _u32,
                             _vp, _i64, _vp],
@@ -85,6 +86,7 @@ _SIGNATURES = {
     "stonk_elementwise_loss_fwd_bwd": [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _f32, _vp],
     "stonk_gelu_bwd_bf16": [_vp, _vp, _vp, _i64, _vp],
     "stonk_sumsq_f32": [_vp, _i64, _vp, _vp, _i64, _vp],
+    "stonk_sumsq_f32_plus": [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp],
     "stonk_adamw_step": [_vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _vp, _f32, _f32,
                          _vp, _i32, _i64, _vp],
     "stonk_adamw_step_tiled": [_vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _vp, _f32, _f32,
@@ -154,6 +156,8 @@ def lib():
         handle.stonk_layernorm_bwd_workspace_floats.restype = C.c_int64
         handle.stonk_sumsq_workspace_floats.argtypes = []
         handle.stonk_sumsq_workspace_floats.restype = C.c_int64
+        handle.stonk_gemm_tn_store_tiles.argtypes = [_i32, _i32, _i32, _i32]   # a count (or a negative status), not a launcher
+        handle.stonk_gemm_tn_store_tiles.restype = C.c_int64
         handle.stonk_linkpred_partial_rows.argtypes = []
         handle.stonk_linkpred_partial_rows.restype = C.c_int64
         handle.stonk_kgb_max_steps.argtypes = []
@@ -169,7 +173,7 @@ def lib():
 def exported_symbols():
     return sorted(list(_SIGNATURES) + ["stonk_abi_version", "stonk_layernorm_bwd_workspace_floats",
                                      "stonk_sumsq_workspace_floats", "stonk_unpad_workspace_ints", "stonk_comm_stream",
-                                     "stonk_linkpred_partial_rows", "stonk_kgb_max_steps"])
+                                     "stonk_linkpred_partial_rows", "stonk_kgb_max_steps", "stonk_gemm_tn_store_tiles"])
 
 
 def check(status: int, name: str) -> None:

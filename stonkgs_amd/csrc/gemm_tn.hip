@@ -23,6 +23,7 @@
 int stonk_gemm256_tn_launch(const stonk_gemm::GemmArgs& a, hipStream_t st);
 int stonk_gemm_tn_a4_launch(const stonk_gemm::GemmArgs& a, hipStream_t st);
 int stonk_gemm_tn_a4_store_launch(const stonk_gemm::GemmArgs& a, hipStream_t st);   // gemm_tn_a4_store.hip
+int stonk_gemm_tn_a4_store_sumsq_launch(const stonk_gemm::GemmArgs& a, hipStream_t st);   // gemm_tn_a4_store_sumsq.hip (a.aux = the slots)
 
 namespace {
 
@@ -43,6 +44,7 @@ struct TnArgs {
   int M, N, K;     // M', N', token count (capacity)
   float alpha;
   int split_k;
+  float* tile_sumsq;   // (gemm_tn_store_sumsq_kernel only) one slot per output tile, row_tile * col_tiles + col_tile
 };
 
 __device__ __forceinline__ int row_swz(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
@@ -52,8 +54,12 @@ typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
 // STORE: the launch has ONE K split, so every output element has exactly one producer - the epilogue writes acc * alpha
 // (and the bias sums) with plain stores instead of adding them into a zeroed buffer, and a launch whose device-side token
 // count leaves no K tile still defines every element (zeros).
-template <bool STORE>
-__global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const TnArgs p) {
+// SUMSQ (with STORE): the workgroup also leaves the sum of the squares of the 128 x 128 values it stored in its tile's slot, in
+// a fixed order - a lane's values in epilogue order (a tree per 16-row block, the blocks one after the other), the wave
+// butterfly, the four waves in index order - so that the gradient-norm pass need not read them back. The accumulator is
+// born after the K loop.
+template <bool STORE, bool SUMSQ>
+__device__ __forceinline__ void gemm_tn_body(const TnArgs& p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -170,8 +176,10 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const TnArgs p) {
   }
 
   // ---- epilogue: acc[i][j][r] = dW[m0 + wm*64 + i*16 + (lane>>4)*4 + r][n0 + wn*64 + j*16 + (lane&15)]
+  float ss = 0.f;
 #pragma unroll
-  for (int i = 0; i < 4; ++i)
+  for (int i = 0; i < 4; ++i) {
+    float sq[4][4];   // (SUMSQ: added up as a tree per 16-row block, the four blocks one after the other)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int m = m0 + wm * 64 + i * 16 + (lane >> 4) * 4 + r;
@@ -180,19 +188,52 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const TnArgs p) {
         const int n = n0 + wn * 64 + j * 16 + (lane & 15);
         if constexpr (STORE) p.C[(long)m * p.ldc + n] = acc[i][j][r] * p.alpha;
         else atomicAdd(p.C + (long)m * p.ldc + n, acc[i][j][r] * p.alpha);
+        if constexpr (SUMSQ) {
+          const float v = acc[i][j][r] * p.alpha;
+          sq[r][j] = v * v;
+        }
       }
       if (want_bias && wn == 0 && (lane & 15) == 0) {
         if constexpr (STORE) p.bias[m] = accb[i][r] * p.alpha;
         else atomicAdd(p.bias + m, accb[i][r] * p.alpha);
       }
     }
+    if constexpr (SUMSQ) {
+      float sr[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) sr[r] = (sq[r][0] + sq[r][1]) + (sq[r][2] + sq[r][3]);
+      ss += (sr[0] + sr[1]) + (sr[2] + sr[3]);
+    }
+  }
+  if constexpr (SUMSQ) {
+    float* part = (float*)smem;   // (the operand images are dead once every wave is past its last K step)
+    ss = wave_sum(ss);
+    __syncthreads();
+    if (lane == 0) part[wave] = ss;
+    __syncthreads();
+    if (tid == 0) p.tile_sumsq[rt * ntn + ct] = ((part[0] + part[1]) + part[2]) + part[3];
+  }
 }
+
+template <bool STORE>
+__global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const TnArgs p) {
+  gemm_tn_body<STORE, false>(p);
+}
+__global__ __launch_bounds__(256, 2) void gemm_tn_store_sumsq_kernel(const TnArgs p) { gemm_tn_body<true, true>(p); }
 
 }  // namespace
 
 // shared body of stonk_gemm_tn_bf16 (atomic accumulate) and stonk_gemm_tn_bf16_store (one K split, plain stores)
+// Output tiles of the kernel a store launch is routed to (256 x 256 for split_k <= 0, else 128 x 128)
+static long gemm_tn_store_tiles(int M, int N, int split_k) {
+  return split_k <= 0 ? (long)((M + 255) / 256) * ((N + 255) / 256) : (long)(M / BM) * (N / BN);
+}
+
+// `tile_sumsq` (store only, nullable): n_slots floats for the per-tile sums of squares - the launch then takes the kernels
+// that leave them
 static int gemm_tn_route(const void* dY, int64_t lda, const void* X, int64_t ldb, float* dW, int64_t ldc, float* dbias,
-                         int M, int N, int K, float alpha, int split_k, const int* k_dev, void* stream, bool store) {
+                         int M, int N, int K, float alpha, int split_k, const int* k_dev, void* stream, bool store,
+                         float* tile_sumsq = nullptr, int64_t n_slots = 0, bool dry = false) {
   STONK_CHECK_ARG(dY && X && dW, STONK_EINVAL);
   STONK_CHECK_ARG(M > 0 && N > 0 && K > 0 && M % BM == 0 && N % BN == 0, STONK_ESHAPE);
   STONK_CHECK_ARG(lda % 8 == 0 && ldb % 8 == 0, STONK_EALIGN);
@@ -226,7 +267,11 @@ static int gemm_tn_route(const void* dY, int64_t lda, const void* X, int64_t ldb
       STONK_CHECK_ARG(sk == 1 && split_k != -1, STONK_ESHAPE);
       // (this kernel shares the bias sums out over the column tiles: one producer per element only with a single one)
       STONK_CHECK_ARG(!dbias || N <= 256, STONK_ESHAPE);
-      return stonk_gemm_tn_a4_store_launch(g, (hipStream_t)stream);
+      if (dry) return STONK_OK;
+      if (!tile_sumsq) return stonk_gemm_tn_a4_store_launch(g, (hipStream_t)stream);
+      STONK_CHECK_ARG(n_slots >= gemm_tn_store_tiles(M, N, split_k), STONK_EINVAL);
+      g.aux = (bf16*)tile_sumsq;
+      return stonk_gemm_tn_a4_store_sumsq_launch(g, (hipStream_t)stream);
     }
     return split_k == -1 ? stonk_gemm256_tn_launch(g, (hipStream_t)stream) : stonk_gemm_tn_a4_launch(g, (hipStream_t)stream);
   }
@@ -236,9 +281,13 @@ static int gemm_tn_route(const void* dY, int64_t lda, const void* X, int64_t ldb
   const int nk = (K + BK - 1) / BK;
   a.split_k = split_k < nk ? split_k : nk;
   const long tiles = (long)(M / BM) * (N / BN) * a.split_k;
+  a.tile_sumsq = tile_sumsq;
   if (store) {
     STONK_CHECK_ARG(a.split_k == 1, STONK_ESHAPE);
-    return stonk_gemm::launch_with_lds<gemm_tn_kernel<true>, TN_LDS>(a, (int)tiles, 256, (hipStream_t)stream);
+    if (dry) return STONK_OK;
+    if (!tile_sumsq) return stonk_gemm::launch_with_lds<gemm_tn_kernel<true>, TN_LDS>(a, (int)tiles, 256, (hipStream_t)stream);
+    STONK_CHECK_ARG(n_slots >= tiles, STONK_EINVAL);
+    return stonk_gemm::launch_with_lds<gemm_tn_store_sumsq_kernel, TN_LDS>(a, (int)tiles, 256, (hipStream_t)stream);
   }
   return stonk_gemm::launch_with_lds<gemm_tn_kernel<false>, TN_LDS>(a, (int)tiles, 256, (hipStream_t)stream);
 }
@@ -256,4 +305,24 @@ extern "C" int stonk_gemm_tn_bf16_store(const void* dY, int64_t lda, const void*
                                         float* dbias, int M, int N, int K, float alpha, int split_k, const int* k_dev,
                                         void* stream) {
   return gemm_tn_route(dY, lda, X, ldb, dW, ldc, dbias, M, N, K, alpha, split_k, k_dev, stream, true);
+}
+
+// stonk_gemm_tn_bf16_store that also writes, for every output tile of the kernel it routes to (256 x 256 for split_k <= 0,
+// else 128 x 128), the sum of the squares of the values it stored: tile_sumsq[row_tile * col_tiles + col_tile]. Every slot is
+// written by every launch (zeros when the device-side token count leaves no K tile), in a fixed order of summation.
+extern "C" int stonk_gemm_tn_bf16_store_sumsq(const void* dY, int64_t lda, const void* X, int64_t ldb, float* dW,
+                                              int64_t ldc, float* dbias, int M, int N, int K, float alpha, int split_k,
+                                              const int* k_dev, float* tile_sumsq, int64_t n_slots, void* stream) {
+  STONK_CHECK_ARG(tile_sumsq && n_slots >= 0, STONK_EINVAL);
+  STONK_CHECK_ARG((uintptr_t)tile_sumsq % 4 == 0, STONK_EALIGN);
+  return gemm_tn_route(dY, lda, X, ldb, dW, ldc, dbias, M, N, K, alpha, split_k, k_dev, stream, true, tile_sumsq, n_slots);
+}
+
+// Slots a stonk_gemm_tn_bf16_store_sumsq launch of this shape writes, or the (negative) status with which the store entry
+// refuses the shape. Nothing is launched; operands are taken as present, aligned and dense (lda = M, ldb = ldc = N).
+extern "C" int64_t stonk_gemm_tn_store_tiles(int M, int N, int K, int split_k) {
+  static const int dummy = 0;   // (any aligned non-null address: a dry run reads nothing)
+  const void* q = (const void*)(((uintptr_t)&dummy + 4096) & ~(uintptr_t)15);
+  const int rc = gemm_tn_route(q, M, q, N, (float*)q, N, nullptr, M, N, K, 1.f, split_k, nullptr, nullptr, true, nullptr, 0, true);
+  return rc != STONK_OK ? rc : gemm_tn_store_tiles(M, N, split_k);
 }

@@ -24,11 +24,22 @@
 // shape instead of adding it into a zeroed buffer, the bias sums are stored too (the launcher admits a bias only with ONE
 // column tile, where the bias duty below puts every K tile on that tile), and a device-side token count that leaves no K
 // tile makes every work item store zeros.
+//
+// STONK_TN_A4_STORE = 2 (gemm_tn_a4_store_sumsq.hip): the store kernel that also leaves, per output tile, the sum of the
+// squares of what it stored (slot row_tile * col_tiles + col_tile of `aux`, here a float array): the gradient-norm pass
+// need not read these values back. The order of the sum is fixed - a lane's values in epilogue order (a tree over the 32
+// values of a row block, the eight blocks one after the other), the wave butterfly, the four waves in index order - so a
+// slot is a function of the inputs alone, whatever the grid. The accumulator is born after the K loop (one VGPR of the
+// epilogue); the waves meet at one raw barrier per tile behind an LDS word each (16 bytes past the operand images), with
+// no wait for the stores or the next item's operand loads in flight.
 #include "gemm_common.h"
 #ifndef STONK_TN_A4_STORE
 #define STONK_TN_A4_STORE 0
 #endif
-#if STONK_TN_A4_STORE
+#if STONK_TN_A4_STORE == 2
+#define STONK_TN_A4_KERNEL gemm_tn_a4_store_sumsq_kernel
+#define STONK_TN_A4_LAUNCH stonk_gemm_tn_a4_store_sumsq_launch
+#elif STONK_TN_A4_STORE
 #define STONK_TN_A4_KERNEL gemm_tn_a4_store_kernel
 #define STONK_TN_A4_LAUNCH stonk_gemm_tn_a4_store_launch
 #else
@@ -46,7 +57,8 @@ namespace {
 
 constexpr int BM = 256, BN = 256, BK = 64;
 constexpr int IMG_BYTES = BK * 512;            // one operand of one K tile: 64 token rows x 512 B = 32 KiB
-constexpr int LDS_BYTES = 4 * IMG_BYTES;       // two stages x (A image + B image)
+constexpr int IMG_LDS = 4 * IMG_BYTES;         // two stages x (A image + B image)
+constexpr int LDS_BYTES = IMG_LDS + (STONK_TN_A4_STORE == 2 ? 16 : 0);   // (+ the four waves' partial sums of squares)
 
 typedef __attribute__((ext_vector_type(4))) int i32x4;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
@@ -87,6 +99,9 @@ __global__ __launch_bounds__(256, 1) void STONK_TN_A4_KERNEL(const GemmArgs p) {
         if (m < M && n < N) ((float*)p.C)[(long)m * ldc0 + n] = 0.f;
       }
       if (p.bias && ct == 0 && rt * BM + tid < M) ((float*)p.bias)[rt * BM + tid] = 0.f;
+#if STONK_TN_A4_STORE == 2
+      if (tid == 0) ((float*)p.aux)[rt * ntn + ct] = 0.f;
+#endif
     }
     return;
   }
@@ -256,6 +271,9 @@ __global__ __launch_bounds__(256, 1) void STONK_TN_A4_KERNEL(const GemmArgs p) {
       const int n = wn0 + 32 * jp + (lane & 31);
       coff[jp] = n * 4 + (n < N ? 0 : 0x40000000);
     }
+#if STONK_TN_A4_STORE == 2
+    float ss = 0.f;   // this lane's share of the tile's sum of squares: values that are stored (row < M', column < N') only
+#endif
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       float xs[4][4], ys[4][4];
@@ -281,12 +299,21 @@ __global__ __launch_bounds__(256, 1) void STONK_TN_A4_KERNEL(const GemmArgs p) {
                      "+v"(ys[3][0]), "+v"(ys[3][1]), "+v"(ys[3][2]), "+v"(ys[3][3]));
 #undef STONK_A4_SWAP4
       const int mrow = wm0 + 16 * i + 8 * (lane >> 5);
+#if STONK_TN_A4_STORE == 2
+      float sq[4][4];   // (added up as a tree per row block, the eight row blocks one after the other: a short chain)
+#endif
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int ro = (mrow + e) * ldc_b, ro4 = (mrow + 4 + e) * ldc_b;
 #pragma unroll
         for (int jp = 0; jp < 4; ++jp) {
-#if STONK_TN_A4_STORE
+#if STONK_TN_A4_STORE == 2
+          const float vx = xs[jp][e] * p.alpha, vy = ys[jp][e] * p.alpha;
+          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(vx), rC, ro + coff[jp], 0, 0);
+          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(vy), rC, ro4 + coff[jp], 0, 0);
+          const bool col_in = coff[jp] < 0x40000000;
+          sq[e][jp] = ((col_in && mrow + e < M) ? vx * vx : 0.f) + ((col_in && mrow + 4 + e < M) ? vy * vy : 0.f);
+#elif STONK_TN_A4_STORE
           __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(xs[jp][e] * p.alpha), rC, ro + coff[jp], 0, 0);
           __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(ys[jp][e] * p.alpha), rC, ro4 + coff[jp], 0, 0);
 #else
@@ -295,6 +322,14 @@ __global__ __launch_bounds__(256, 1) void STONK_TN_A4_KERNEL(const GemmArgs p) {
 #endif
         }
       }
+#if STONK_TN_A4_STORE == 2
+      {
+        float se[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) se[e] = (sq[e][0] + sq[e][1]) + (sq[e][2] + sq[e][3]);
+        ss += (se[0] + se[1]) + (se[2] + se[3]);
+      }
+#endif
       // bias gradient of this block's 16 features: every column of the extra accumulator holds the same sums
 #if STONK_TN_A4_STORE
       if (want_bias && wc == 0 && ct == 0) {
@@ -312,6 +347,16 @@ __global__ __launch_bounds__(256, 1) void STONK_TN_A4_KERNEL(const GemmArgs p) {
       }
 #endif
     }
+#if STONK_TN_A4_STORE == 2
+    {
+      // (the previous tile's reader of these four words is two barriers or more behind: every K loop has them)
+      volatile float* part = (volatile float*)(smem + IMG_LDS);
+      ss = wave_sum(ss);
+      if (lane == 0) part[wave] = ss;
+      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      if (tid == 0) ((float*)p.aux)[(cw.m0 / BM) * ntn + cw.n0 / BN] = ((part[0] + part[1]) + part[2]) + part[3];
+    }
+#endif
     if (!more) break;
     cwi = nwi;
     cw = nw;

@@ -23,8 +23,16 @@ namespace {
 #endif
 constexpr int SUMSQ_MAX_BLOCKS = STONK_SUMSQ_BLOCKS;
 
+// `extra` (nullable, stonk_sumsq_f32_plus): n_extra sums of squares somebody else has taken already (the per-tile sums a
+// store-mode weight gradient leaves, stonk_gemm_tn_bf16_store_sumsq). The last block adds them to its total in index order,
+// behind the partial slots - still one fixed order, and no launch of its own on the serial path: the extras are cut into 64
+// consecutive runs of ceil(n_extra / 64), lane r of the first wave adds run r up element by element, and the 64 run sums
+// are added to the total one after the other. All of it in fp64, rounded to fp32 once at the end: in fp32, a thousand
+// small addends each rounded at the size of the running total left the norm 6e-6 off (90 ulp; the full pass is within
+// one). (One thread adding all 3 414 slots of the flagship's decoders one by one was a dependent chain of 35 us.)
 __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ x, long n, float* __restrict__ out,
-                                                    float* __restrict__ g_sumsq_part, unsigned* __restrict__ ticket) {
+                                                    float* __restrict__ g_sumsq_part, unsigned* __restrict__ ticket,
+                                                    const float* __restrict__ extra, long n_extra) {
   float acc = 0.f;
   const long n4 = n >> 2;
   const long stride = (long)gridDim.x * 256;
@@ -66,8 +74,22 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ x,
   tot = wave_sum(tot);
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = tot;
   __syncthreads();
+  tot = (part[0] + part[1]) + (part[2] + part[3]);
+  if (n_extra > 0) {   // (a kernel argument: uniform)
+    __shared__ double run[64];
+    if (threadIdx.x < 64) {
+      const long per = (n_extra + 63) >> 6, lo = threadIdx.x * per, hi = lo + per < n_extra ? lo + per : n_extra;
+      double a = 0.0;
+      for (long i = lo; i < hi; ++i) a += (double)extra[i];
+      run[threadIdx.x] = a;
+    }
+    __syncthreads();
+    double wide = tot;
+    for (int r = 0; r < 64; ++r) wide += run[r];
+    tot = (float)wide;
+  }
   if (threadIdx.x == 0) {
-    atomicAdd(out, (part[0] + part[1]) + (part[2] + part[3]));
+    atomicAdd(out, tot);
     __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
   }
 }
@@ -481,16 +503,23 @@ inline int ew_grid(long n) {
 
 extern "C" int64_t stonk_sumsq_workspace_floats(void) { return SUMSQ_MAX_BLOCKS + 1; }
 
-extern "C" int stonk_sumsq_f32(const float* x, int64_t n, float* out_accum, float* workspace, int64_t ws_floats,
-                               void* stream) {
+// *out_accum += sum(x^2) + extra[0] + extra[1] + ... (stonk_sumsq_f32: no extras; then an empty x launches nothing)
+extern "C" int stonk_sumsq_f32_plus(const float* x, int64_t n, float* out_accum, float* workspace, int64_t ws_floats,
+                                    const float* extra, int64_t n_extra, void* stream) {
   STONK_CHECK_ARG(x && out_accum && workspace && n >= 0, STONK_EINVAL);
+  STONK_CHECK_ARG(n_extra >= 0 && (extra || n_extra == 0), STONK_EINVAL);
   STONK_CHECK_ARG(ws_floats >= SUMSQ_MAX_BLOCKS + 1, STONK_EINVAL);
-  STONK_CHECK_ARG((uintptr_t)x % 16 == 0 && (uintptr_t)workspace % 4 == 0, STONK_EALIGN);
-  if (n == 0) return STONK_OK;
+  STONK_CHECK_ARG((uintptr_t)x % 16 == 0 && (uintptr_t)workspace % 4 == 0 && (uintptr_t)extra % 4 == 0, STONK_EALIGN);
+  if (n == 0 && n_extra == 0) return STONK_OK;
   const int grid = ew_grid(n) < SUMSQ_MAX_BLOCKS ? ew_grid(n) : SUMSQ_MAX_BLOCKS;
   hipLaunchKernelGGL(sumsq_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, (long)n, out_accum, workspace,
-                     (unsigned*)(workspace + SUMSQ_MAX_BLOCKS));
+                     (unsigned*)(workspace + SUMSQ_MAX_BLOCKS), extra, (long)n_extra);
   return stonk_launch_status();
+}
+
+extern "C" int stonk_sumsq_f32(const float* x, int64_t n, float* out_accum, float* workspace, int64_t ws_floats,
+                               void* stream) {
+  return stonk_sumsq_f32_plus(x, n, out_accum, workspace, ws_floats, nullptr, 0, stream);
 }
 
 extern "C" int stonk_adamw_step(float* p, float* g, float* m, float* v, void* p_bf16, int64_t n, float lr, float beta1,

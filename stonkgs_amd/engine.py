@@ -144,6 +144,17 @@ class Engine:
         self.store_first = False
         self.grad_stale: set = set()
         self.store_log = collections.deque(maxlen=64)   # (name, status) of the latest store-mode attempts (tests, debugging)
+        # Sums of squares from the store epilogue (stonk_gemm_tn_bf16_store_sumsq): while `store_sumsq`
+        # is set (by a trainer whose gradient norm is the norm of ONE backward on ONE rank) a store launch also leaves its
+        # output tiles' sums of squares in its region of one slot buffer, and the gradient-norm pass need not read that
+        # gradient back. `sumsq_valid`: the weights whose slots are THIS step's - set by the store launch that returned OK,
+        # dropped by any other launch into the same gradient and when the optimizer has taken them (`take_wgrad_sumsq`).
+        # `norm_from_epilogue` = False: store launches never write slots (the norm reads the whole buffer, as it did).
+        self.norm_from_epilogue = True
+        self.store_sumsq = False
+        self.sumsq_valid: set = set()
+        self._sumsq_tiles: Dict[str, int] = {}
+        self._sumsq_buf: Optional[torch.Tensor] = None
         # Inputs-only backward (`input_gradients`, which alone sets it): the chain of dgrad GEMMs, LayerNorm and attention
         # backward runs down to d(embedding sum) and nothing is written to the gradient buffer - `wgrad` returns at once,
         # `ln_bwd` passes null dgamma / dbeta, the small linear layers' weight gradients go to scratch, stonk_embed_grad
@@ -301,6 +312,7 @@ class Engine:
         has one K split - no atomics, and the optimizer does not zero the span afterwards."""
         if self._inputs_only:   # (before the store-mode bookkeeping: `store_log`, `grad_stale`, `store_first` do not move)
             return
+        self.sumsq_valid.discard(name)   # whatever this launch does to the gradient, an earlier launch's sums are not its norm
         side = self.overlap_wgrad
         split = self._split_k(M_out, N_in, T, side)
         # (the fork: dy and x are complete on the main stream at this point)
@@ -313,10 +325,16 @@ class Engine:
             # "the routing splits K at this shape" (anything else both entries refuse alike, and the call below raises)
             can_store = db is None and dW.stride(0) >= N_in and M_out * dW.stride(0) * 4 < 1 << 31
             if name is not None and self.store_first and name in self.store_names and can_store:
-                rc = hip.lib().stonk_gemm_tn_bf16_store(*args)
+                slots = self._sumsq_slots(name, M_out, N_in, T, split) if self.store_sumsq and self.norm_from_epilogue else None
+                if slots is None:
+                    rc = hip.lib().stonk_gemm_tn_bf16_store(*args)
+                else:
+                    rc = hip.lib().stonk_gemm_tn_bf16_store_sumsq(*args[:-1], slots.data_ptr(), slots.numel(), args[-1])
                 self.store_log.append((name, rc))
                 if rc == hip.OK:
                     self.grad_stale.discard(name)
+                    if slots is not None:
+                        self.sumsq_valid.add(name)
                     return
                 if rc != hip.ESHAPE:
                     hip.check(rc, "stonk_gemm_tn_bf16_store")
@@ -324,6 +342,35 @@ class Engine:
                 dW.zero_()
                 self.grad_stale.discard(name)
             hip.call("stonk_gemm_tn_bf16", *args)
+
+    def _sumsq_slots(self, name, M, N, K, split) -> Optional[torch.Tensor]:
+        """The region of the slot buffer that the store launch of weight `name` fills (one float per output tile), or None
+        when the store entry refuses the shape (the plain attempt then records its status). Regions lie in the order of
+        `store_names`, so that all of them together are ONE contiguous array of extras for stonk_sumsq_f32_plus."""
+        n = int(hip.lib().stonk_gemm_tn_store_tiles(M, N, K, split))
+        if n <= 0:
+            return None
+        at = self.store_names.index(name)
+        if self._sumsq_tiles.get(name) != n:   # (first use, or another shape: the regions behind this one move)
+            self._sumsq_tiles[name] = n
+            self.sumsq_valid.difference_update(self.store_names[at + 1:])
+        total = sum(self._sumsq_tiles.values())
+        if self._sumsq_buf is None or self._sumsq_buf.numel() < total:
+            self._sumsq_buf = torch.zeros(max(total, 16384), dtype=F32, device=self.device)
+            self.sumsq_valid.clear()
+        first = sum(self._sumsq_tiles.get(k, 0) for k in self.store_names[:at])
+        return self._sumsq_buf[first:first + n]
+
+    def take_wgrad_sumsq(self):
+        """([lo, hi) spans of the flat gradient buffer whose sum of squares is already known, those sums: one device array) when
+        EVERY weight of `store_names` was stored with its sums by this step's backward, else None. Either way the slots are
+        used up: a later step must write its own."""
+        ok = bool(self.store_names) and self.sumsq_valid == set(self.store_names)
+        self.sumsq_valid.clear()
+        if not ok:
+            return None
+        total = sum(self._sumsq_tiles[k] for k in self.store_names)
+        return sorted(self.P.span(k) for k in self.store_names), self._sumsq_buf[:total]
 
     def _gather_rows(self, src, rd_rows, cnt, dst, cap) -> None:
         """dst[i] = src[rd_rows[i]] for the first cnt[0] rows (a device-side count); rows from the count up to the next

@@ -86,7 +86,7 @@ def linear_schedule_lr(base_lr: float, step: int, max_steps: int, warmup: int = 
 
 
 class FusedAdamW:
-    """clip_grad_norm_ + AdamW + zero_grad over the model's flat fp32 buffers in two kernel launches - or, with `spans`
+    """clip_grad_norm_ + AdamW + zero_grad over the model's flat fp32 buffers in a few kernel launches - or, with `spans`
     (optimizer sharding: the [lo, hi) pieces of the flat buffer this rank owns), the same per piece with m / v stored for
     the owned pieces only."""
 
@@ -106,6 +106,9 @@ class FusedAdamW:
         # partial sums + ticket of the fixed-order grad-norm reduction (zeroed once; the kernel leaves it ready)
         self.norm_ws = torch.zeros(int(hip.lib().stonk_sumsq_workspace_floats()), dtype=torch.float32, device=dev)
         self.step_count = 0
+        # how the latest gradient norm was taken: "full pass" = sum of squares over the whole buffer (this rank's pieces),
+        # "epilogue" = over the complement of the spans whose sums the weight-gradient kernels had left (`known`)
+        self.norm_route = None
         self._decay_spans = None   # device [n, 2] int64 of the decayed tensors' [lo, hi) offsets (built on first use)
 
     def _pieces(self):
@@ -118,14 +121,30 @@ class FusedAdamW:
             acc += hi - lo
         return out
 
-    def accumulate_grad_norm_sq(self) -> None:
+    def accumulate_grad_norm_sq(self, known=None) -> None:
         """gnorm_sq = sum of squares of the gradient over this rank's pieces (the whole buffer without sharding) - in a
-        fixed order, so that replicas holding the same gradients get the same bits."""
+        fixed order, so that replicas holding the same gradients get the same bits.
+        `known` (Engine.take_wgrad_sumsq(); unsharded only): (sorted disjoint [lo, hi) spans, device array of sums of squares
+        that add up to those spans' share) - the pass reads the complement of the spans only and its last launch adds the
+        sums in index order: still one fixed order, but another one than the full pass has."""
         s, st = self.store, hip.stream_ptr()
         self.gnorm_sq.zero_()
-        for off, _, n in self._pieces():
-            hip.call("stonk_sumsq_f32", s.grad.data_ptr() + 4 * off, n, self.gnorm_sq.data_ptr(), self.norm_ws.data_ptr(),
-                     self.norm_ws.numel(), st)
+        pieces, extra = self._pieces(), None
+        if known is not None:
+            if self.spans is not None:
+                raise ValueError("sums of squares from the weight-gradient kernels: not with a sharded optimizer")
+            spans, extra = known
+            pieces, pos = [], 0
+            for lo, hi in list(spans) + [(s.numel, s.numel)]:
+                if lo > pos:
+                    pieces.append((pos, pos, lo - pos))
+                pos = max(pos, hi)
+            pieces = pieces or [(0, 0, 0)]   # (nothing left to read: one launch for the sums alone)
+        self.norm_route = "full pass" if known is None else "epilogue"
+        for i, (off, _, n) in enumerate(pieces):
+            ex = extra if i == len(pieces) - 1 else None
+            hip.call("stonk_sumsq_f32_plus", s.grad.data_ptr() + 4 * off, n, self.gnorm_sq.data_ptr(), self.norm_ws.data_ptr(),
+                     self.norm_ws.numel(), hip.ptr(ex), 0 if ex is None else ex.numel(), st)
 
     def _decay_table(self):
         if self._decay_spans is None:
@@ -504,19 +523,25 @@ class Trainer:
         # (nothing has accumulated into this step's gradients yet: the decoders' weight gradients may be stored. Only for
         # THIS backward - one that somebody else drives on the same model afterwards accumulates, as autograd expects)
         model.engine.store_first = gas == 1 or self._micro % gas == 1
+        # (... and where this ONE backward on ONE rank is the whole gradient, the stored tiles' sums of squares are their
+        # share of the gradient norm: the norm pass skips what the store epilogue has summed already)
+        epilogue_norm = gas == 1 and self.optimizer.spans is None and self.world == 1 and not self.args.bucket_grad_norm
+        model.engine.store_sumsq = epilogue_norm
         try:
             with model.engine.block("K1-K15 forward + backward"):
                 loss = model.forward_backward(inputs, gscale=1.0 / gas, on_segment_done=hook)
         finally:
-            model.engine.store_first = False
+            model.engine.store_first = model.engine.store_sumsq = False
         if last:
             lr = linear_schedule_lr(self.args.learning_rate, self.global_step, self.args.max_steps, self.args.warmup_steps)
             with model.engine.optimizer_stream(self.args.optimizer_overlap), model.engine.block("K16-K17 all-reduce wait + AdamW"):
                 scale = self.sync.finish()
                 opt = self.optimizer
                 opt.step_count += 1
+                known = model.engine.take_wgrad_sumsq()     # (None unless both decoders stored with their sums just now)
                 if not self.sync.take_grad_norm_sq(opt.gnorm_sq):   # (bucket partials taken during backward)
-                    opt.accumulate_grad_norm_sq()           # replicated: the whole buffer; sharded: this rank's pieces ...
+                    # replicated: the whole buffer, or what the store epilogues have not summed; sharded: this rank's pieces ...
+                    opt.accumulate_grad_norm_sq(known if epilogue_norm else None)
                 self.sync.all_reduce_scalar(opt.gnorm_sq)   # ... summed over the ranks (a no-op when replicated)
                 if self.sync.shard:
                     opt.apply_update(lr, grad_scale=scale)
