@@ -66,6 +66,9 @@ class GemmTimer:
 
 
 class Engine:
+    ERR_BITS = ERR_BITS      # what check_errors says for each bit of the kernels' error word ...
+    KEY_ERROR_BITS = 1       # ... and which of them make it a KeyError instead of an IndexError
+
     def __init__(self, cfg: STonKGsConfig, store: FlatStore, backbone: FlatStore, n_backbone_layers: int, device):
         cfg.validate_for_hip()
         hip.lib()  # fail loudly, now, if the extension is missing
@@ -277,8 +280,8 @@ class Engine:
         e = int(self.err.item())
         if e:
             self.err.zero_()
-            msgs = [m for b, m in ERR_BITS.items() if e & b]
-            if e & 1:
+            msgs = [m for b, m in self.ERR_BITS.items() if e & b]
+            if e & self.KEY_ERROR_BITS:
                 raise KeyError("; ".join(msgs))
             raise IndexError("; ".join(msgs))
 
@@ -411,7 +414,7 @@ class Engine:
         """bf16 mirrors (if the optimizer has not just written them) and W^T copies for dgrad."""
         st = hip.stream_ptr()
         if bf16_mirror:
-            for s in (self.P, self.BB):
+            for s in (self.P,) if self.BB is None else (self.P, self.BB):
                 hip.call("stonk_cast_f32_to_bf16", s.data.data_ptr(), s.bf16.data_ptr(), s.numel, st)
         self._refresh_wt(st)
 
@@ -1446,7 +1449,7 @@ class Engine:
         self.backward_encoder(dpooled, dseq, sv, notify)
 
 
-TEXT_ERR_BITS = {1: "token id outside [0, vocab_size)", 2: ERR_BITS[2], 16: "class label outside [0, num_labels)"}
+TEXT_ERR_BITS = {**ERR_BITS, 1: "token id outside [0, vocab_size)", 16: "class label outside [0, num_labels)"}
 
 
 class TextEngine(Engine):
@@ -1459,7 +1462,9 @@ class TextEngine(Engine):
     base class's. Only the gather reads the table: it has no W^T copy, and its bf16 mirror is never read."""
 
     WORD = "bert.embeddings.word_embeddings.weight"
-    PADDING_IDX = 0   # BertEmbeddings: nn.Embedding(vocab_size, hidden_size, padding_idx=config.pad_token_id = 0)
+    ERR_BITS = TEXT_ERR_BITS
+    KEY_ERROR_BITS = 0   # an out-of-range token id is an IndexError: what torch's embedding raises
+    PADDING_IDX = 0  # BertEmbeddings: nn.Embedding(vocab_size, hidden_size, padding_idx=config.pad_token_id = 0)
 
     def __init__(self, cfg: STonKGsConfig, store: FlatStore, device):
         super().__init__(cfg, store, None, 0, device)
@@ -1474,12 +1479,6 @@ class TextEngine(Engine):
         self.next_input_ids = None
         return self.kg_table, None
 
-    def refresh_derived(self, bf16_mirror: bool = True) -> None:
-        st = hip.stream_ptr()
-        if bf16_mirror:
-            hip.call("stonk_cast_f32_to_bf16", self.P.data.data_ptr(), self.P.bf16.data_ptr(), self.P.numel, st)
-        self._refresh_wt(st)
-
     def _word_embed_grad(self, dsum, sv) -> None:
         cfg, plan = self.cfg, sv["plan"]
         dword = self.P.grad_view(self.WORD)
@@ -1487,10 +1486,3 @@ class TextEngine(Engine):
                  0 if plan is None else plan["row_of_pos"].data_ptr(), dword.data_ptr(), dword.stride(0), cfg.vocab_size,
                  self.PADDING_IDX, sv["B"], cfg.max_position_embeddings, cfg.hidden_size, self.err.data_ptr(),
                  hip.stream_ptr())
-
-    def check_errors(self) -> None:
-        """As the base class, but an out-of-range token id is an IndexError: what torch's embedding raises."""
-        e = int(self.err.item())
-        if e:
-            self.err.zero_()
-            raise IndexError("; ".join(TEXT_ERR_BITS.get(b, m) for b, m in ERR_BITS.items() if e & b))

@@ -17,7 +17,6 @@ from LOCAL files (``model_type`` is a directory, never a hub name)."""
 from __future__ import annotations
 
 import logging
-import math
 import os
 from typing import Dict, List, Optional
 
@@ -25,31 +24,28 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import _hip as hip
 from . import stonkgs_finetuning as _ft
 from .config import STonKGsConfig
 from .engine import TextEngine
+from .flat_model import FlatBufferModel, SequenceClassifierFront, _load_weights_file
 from .params import FlatStore, _linear, build_bert_tree, trainable_specs
-from .stonkgs_model import (STonKGsForPreTraining, SequenceClassifierOutput, _ClsStepFunction, _load_weights_file)
 
 logger = logging.getLogger(__name__)
 
 WORD = TextEngine.WORD
 
 
-class BertForSequenceClassification(STonKGsForPreTraining):
+class BertForSequenceClassification(SequenceClassifierFront, FlatBufferModel):
     """hf:models/bert/modeling_bert.py BertForSequenceClassification as the reference uses it (:171-173), single-label
-    cross-entropy. Inherits the flat-buffer plumbing of the STonKGs models (gradient views, ``zero_grad``, the autograd
-    bridge, ``state_dict`` / ``save_pretrained``, ``Trainer`` compatibility) and none of their front: no frozen backbone,
-    no entity table, no pre-training heads. ``input_ids`` may be ``[B, L]`` with any ``L <= max_position_embeddings``
-    (the reference pads to the longest text of the split, :176-181): the batch is right-padded to the model's length on
-    the device with mask 0, which the packed-row encoder drops again."""
+    cross-entropy. Shares ``FlatBufferModel`` with the STonKGs models (gradient views, ``zero_grad``, the autograd
+    bridge, ``state_dict`` / ``save_pretrained``, ``Trainer`` compatibility) and the classifier front with the STonKGs
+    fine-tuning model, and has none of the STonKGs front: no frozen backbone, no entity table, no pre-training heads.
+    ``input_ids`` may be ``[B, L]`` with any ``L <= max_position_embeddings`` (the reference pads to the longest text of
+    the split, :176-181): the batch is right-padded to the model's length on the device with mask 0, which the packed-row
+    encoder drops again."""
 
     def __init__(self, config, num_labels: Optional[int] = None, *, device=None, seed: int = 0):
-        nn.Module.__init__(self)
-        if not torch.cuda.is_available():
-            raise hip.StonkHipError("BertForSequenceClassification needs an MI355X: the hot path has no CPU fallback")
-        self._device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        super().__init__(device)
         cfg = STonKGsConfig.from_any(config)
         if num_labels is not None:
             cfg.num_labels = int(num_labels)
@@ -66,45 +62,15 @@ class BertForSequenceClassification(STonKGsForPreTraining):
         self.dropout = nn.Dropout(cfg.hidden_dropout_prob)   # naming only; the engine applies it (classifier dropout =
         self.classifier = _linear(self._store, "classifier", True)   # hidden_dropout_prob: classifier_dropout is None)
         self.engine = TextEngine(cfg, self._store, dev)
-        self._segment_hook = None
-        self._anchor = torch.zeros((), device=dev, requires_grad=True)
         self._init_weights(seed)
-        self._grad_views = {n: p.grad for n, p in self.named_parameters() if p.requires_grad}
+        self._bind_grad_views()
         self.refresh()
 
-    def _init_weights(self, seed: int) -> None:
-        """BERT init (hf _init_weights: N(0, initializer_range) matrices / embeddings with a zero padding row, zero bias,
-        unit LayerNorm)."""
-        g = torch.Generator(device="cpu").manual_seed(seed)
-        std = self.config.initializer_range
-        with torch.no_grad():
-            for name, (off, shape, _) in self._store.index.items():
-                v = self._store.view(name)
-                if "LayerNorm.weight" in name:
-                    v.fill_(1.0)
-                elif name.endswith(".bias"):
-                    v.zero_()
-                else:
-                    v.copy_((torch.randn(shape, generator=g) * std).to(v.device))
-            self._store.view(WORD)[TextEngine.PADDING_IDX].zero_()
+    def _stores(self) -> tuple:
+        return (self._store,)
 
-    # -------------------------------------------------------------- masters <-> derived copies (one store)
-    def refresh(self) -> None:
-        self.engine.refresh_derived(bf16_mirror=True)
-        self._mark_synced()
-
-    def _mark_synced(self, clear_pending: bool = True) -> None:
-        self._synced_versions = (self._store.data._version,)
-        if clear_pending:
-            self._external_step_pending = False
-
-    def _sync_derived(self) -> None:
-        v = (self._store.data._version,)
-        if v == self._synced_versions and not self._external_step_pending:
-            return
-        self._wait_params()
-        self.engine.refresh_derived(bf16_mirror=True)
-        self._mark_synced(clear_pending=v != self._synced_versions)
+    def _after_init_weights(self) -> None:
+        self._store.view(WORD)[TextEngine.PADDING_IDX].zero_()   # hf _init_weights: the embedding's padding row is zero
 
     # -------------------------------------------------------------- loaders
     @classmethod
@@ -132,26 +98,14 @@ class BertForSequenceClassification(STonKGsForPreTraining):
                           f"newly initialized: {missing}. You should probably TRAIN this model on a down-stream task.")
         return model
 
-    @classmethod
-    def from_default_pretrained(cls, **kwargs):
-        raise NotImplementedError("pass a local directory to from_pretrained")
-
     # -------------------------------------------------------------- forward
-    def _prep(self, t):
-        if t is None:
-            return None
-        t = torch.as_tensor(t)
-        if t.device != self._device or t.dtype != torch.long or not t.is_contiguous():
-            t = t.to(device=self._device, dtype=torch.long).contiguous()
-        return t
-
     def _inputs(self, input_ids, attention_mask, token_type_ids):
         """[B, L] -> contiguous int64 [B, S] on the device: right-padded with [PAD] / mask 0 / type 0. No attention mask =
         every given position is attended, as in HF."""
         if input_ids is None:
             raise ValueError("input_ids is required")
         S = self.config.max_position_embeddings
-        ids, am, tt = self._prep(input_ids), self._prep(attention_mask), self._prep(token_type_ids)
+        ids, am, tt = self._long(input_ids), self._long(attention_mask), self._long(token_type_ids)
         if ids.dim() != 2 or ids.shape[1] > S or ids.shape[1] < 1:
             raise ValueError(f"input_ids must be [B, L] with 1 <= L <= {S}")
         if am is None:
@@ -162,35 +116,13 @@ class BertForSequenceClassification(STonKGsForPreTraining):
             tt = None if tt is None else nn.functional.pad(tt, (0, pad))
         return ids, am, tt
 
-    def forward(self, input_ids=None, attention_mask=None, token_type_ids=None, labels=None, return_dict=None):
+    def _cls_inputs(self, input_ids, attention_mask, token_type_ids, labels):
         ids, am, tt = self._inputs(input_ids, attention_mask, token_type_ids)
-        lab = None if labels is None else self._prep(torch.as_tensor(labels).reshape(-1))
-        training = self.training
-        self._sync_derived()
-        need_bwd = lab is not None and torch.is_grad_enabled() and training
-        out = self.engine.forward_cls(ids, am, tt, lab, self.num_labels, training, need_bwd)
-        loss = None
-        if lab is not None:
-            loss = _ClsStepFunction.apply(self._anchor, self, out["loss"]) if need_bwd else out["loss"].clone()
-        logits = out["logits"].clone()
-        if not return_dict:
-            return (loss, logits) if loss is not None else (logits,)
-        return SequenceClassifierOutput(loss=loss, logits=logits, hidden_states=None, attentions=None)
+        lab = None if labels is None else self._long(torch.as_tensor(labels).reshape(-1))
+        return ids, am, tt, lab, None   # (single-label cross-entropy)
 
-    def forward_backward(self, inputs, gscale: float = 1.0, on_segment_done=None):
-        ids, am, tt = self._inputs(inputs["input_ids"], inputs.get("attention_mask"), inputs.get("token_type_ids"))
-        lab = self._prep(torch.as_tensor(inputs["labels"]).reshape(-1))
-        self._sync_derived()
-        out = self.engine.forward_cls(ids, am, tt, lab, self.num_labels, self.training, True)
-        loss = out["loss"].clone()
-        self.engine.backward_cls(gscale, on_segment_done)
-        return loss
-
-    def _stonkgs_only(self, *args, **kwargs):
-        raise NotImplementedError("not available on the text-only model (attention maps, input attributions and the masked "
-                                  "prediction helpers belong to the STonKGs models)")
-
-    encode = attention_maps = input_attributions = evaluate_batch = predict_masked = entity_names = _stonkgs_only
+    def forward(self, input_ids=None, attention_mask=None, token_type_ids=None, labels=None, return_dict=None):
+        return self._classify(*self._cls_inputs(input_ids, attention_mask, token_type_ids, labels), return_dict)
 
 
 # ---------------------------------------------------------------------------------------------------- the driver
@@ -234,7 +166,6 @@ def run_nlp_baseline_classification_cv(train_data_path: str, sep: Optional[str] 
     import pandas as pd
 
     from .stonkgs_for_embeddings import _local_tokenizer
-    from .stonkgs_pretraining import Trainer, TrainingArguments
 
     if model_type is None or not os.path.isdir(model_type):
         raise FileNotFoundError(f"model_type = {model_type!r}: pass the local directory of the pre-trained BERT (hub names "
@@ -263,19 +194,9 @@ def run_nlp_baseline_classification_cv(train_data_path: str, sep: Optional[str] 
         train_ds, test_ds = (INDRAEvidenceDataset(
             tokenizer(evidences_text[ix].tolist(), truncation=True, padding=True, max_length=max_length), labels[ix].tolist())
             for ix in (tr_idx, te_idx))
-        steps_per_epoch = max(1, math.ceil(len(train_ds) / (batch_size * gradient_accumulation)))
-        args = TrainingArguments(learning_rate=lr, max_steps=epochs * steps_per_epoch,
-                                 per_device_train_batch_size=batch_size, gradient_accumulation_steps=gradient_accumulation,
-                                 seed=seed, logging_steps=max(1, steps_per_epoch))
-        model.train()
-        trainer = Trainer(model, args)
-        g = torch.Generator().manual_seed(seed + idx)
-        for _ in range(epochs):                       # RandomSampler order per epoch; the last batch may be ragged
-            perm = torch.randperm(len(train_ds), generator=g).tolist()
-            for lo in range(0, len(perm), batch_size):
-                trainer.training_step(model, _ft._collate([train_ds[i] for i in perm[lo:lo + batch_size]]))
-        model.engine.check_errors()
-        predicted = np.argmax(_ft.predict_logits(model, test_ds, batch_size), axis=1)
+        predicted = np.argmax(_ft.train_and_predict_fold(
+            model, train_ds, test_ds, epochs=epochs, lr=lr, batch_size=batch_size,
+            gradient_accumulation=gradient_accumulation, seed=seed, fold=idx), axis=1)
         model.engine.check_errors()
         f1_scores.append(_ft.weighted_f1_score(labels[te_idx], predicted))
         frames.append(pd.DataFrame({"split": idx, "index": te_idx.tolist(),

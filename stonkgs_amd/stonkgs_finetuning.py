@@ -96,6 +96,25 @@ def predict_logits(model: STonKGsForSequenceClassification, dataset: INDRADatase
     return torch.cat(out).numpy() if out else np.zeros((0, model.num_labels), dtype=np.float32)
 
 
+def train_and_predict_fold(model, train_ds, test_ds, *, epochs: int, lr: float, batch_size: int,
+                           gradient_accumulation: int, seed: int, fold: int) -> np.ndarray:
+    """One cross-validation fold of either classifier: ``Trainer`` steps over ``train_ds`` in RandomSampler order (seeded
+    by ``seed + fold``; linear decay over all steps), then the eval-mode logits of ``test_ds``."""
+    steps_per_epoch = max(1, math.ceil(len(train_ds) / (batch_size * gradient_accumulation)))
+    args = TrainingArguments(learning_rate=lr, max_steps=epochs * steps_per_epoch,
+                             per_device_train_batch_size=batch_size, gradient_accumulation_steps=gradient_accumulation,
+                             seed=seed, logging_steps=max(1, steps_per_epoch))
+    model.train()
+    trainer = Trainer(model, args)
+    g = torch.Generator().manual_seed(seed + fold)
+    for _ in range(epochs):                       # RandomSampler order per epoch; the last batch may be ragged
+        perm = torch.randperm(len(train_ds), generator=g).tolist()
+        for lo in range(0, len(perm), batch_size):
+            trainer.training_step(model, _collate([train_ds[i] for i in perm[lo:lo + batch_size]]))
+    model.engine.check_errors()
+    return predict_logits(model, test_ds, batch_size)
+
+
 def run_sequence_classification_cv(fine_tuning_data, labels: Optional[Sequence[int]] = None, *,
                                    model_factory: Callable[[int], STonKGsForSequenceClassification],
                                    class_column_name: str = "labels", epochs: int = 3, lr: float = 5e-5,
@@ -117,19 +136,9 @@ def run_sequence_classification_cv(fine_tuning_data, labels: Optional[Sequence[i
         tr_idx, te_idx = ind["train_idx"], ind["test_idx"]
         train_ds = INDRADataset({k: [v[i] for i in tr_idx] for k, v in cols.items()}, y[tr_idx].tolist())
         test_ds = INDRADataset({k: [v[i] for i in te_idx] for k, v in cols.items()}, y[te_idx].tolist())
-        steps_per_epoch = max(1, math.ceil(len(train_ds) / (batch_size * gradient_accumulation)))
-        args = TrainingArguments(learning_rate=lr, max_steps=epochs * steps_per_epoch,
-                                 per_device_train_batch_size=batch_size, gradient_accumulation_steps=gradient_accumulation,
-                                 seed=seed, logging_steps=max(1, steps_per_epoch))
-        model.train()
-        g = torch.Generator().manual_seed(seed + idx)
-        trainer = Trainer(model, args)
-        for _ in range(epochs):                       # RandomSampler order per epoch; the last batch may be ragged
-            perm = torch.randperm(len(train_ds), generator=g).tolist()
-            for lo in range(0, len(perm), batch_size):
-                trainer.training_step(model, _collate([train_ds[i] for i in perm[lo:lo + batch_size]]))
-        model.engine.check_errors()
-        predicted = np.argmax(predict_logits(model, test_ds, batch_size), axis=1)
+        predicted = np.argmax(train_and_predict_fold(
+            model, train_ds, test_ds, epochs=epochs, lr=lr, batch_size=batch_size,
+            gradient_accumulation=gradient_accumulation, seed=seed, fold=idx), axis=1)
         f1_scores.append(weighted_f1_score(y[te_idx], predicted))
         frames.append(pd.DataFrame({"split": idx, "index": te_idx.tolist(), "predicted_label": predicted.tolist(),
                                     "true_label": y[te_idx].tolist()}))

@@ -25,6 +25,8 @@ from torch import nn
 from . import _hip as hip
 from .config import STonKGsConfig
 from .engine import Engine
+from .flat_model import (FlatBufferModel, SequenceClassifierFront, SequenceClassifierOutput,  # noqa: F401
+                         _load_weights_file, _StepFunction)
 from .params import (FlatStore, _Node, _linear, _param, backbone_specs, build_bert_tree, pretraining_head_specs,
                      trainable_specs)
 
@@ -112,25 +114,7 @@ class STonKGsELMPredictionHead(_Node):
         self.decoder = dec
 
 
-class _StepFunction(torch.autograd.Function):
-    """Makes ``loss.backward()`` (HF Trainer / accelerate) drive the engine's hand-written backward."""
-
-    @staticmethod
-    def forward(ctx, anchor, model, loss):
-        ctx.model = model
-        return loss.clone()
-
-    @staticmethod
-    def backward(ctx, dloss):
-        model = ctx.model
-        model._prepare_grads_for_autograd()
-        model.engine.backward(float(dloss), model._segment_hook)
-        model._reattach_grads()
-        model._external_step_pending = True   # whoever called loss.backward() steps the masters with its own optimizer
-        return None, None, None
-
-
-class STonKGsForPreTraining(nn.Module):
+class STonKGsForPreTraining(FlatBufferModel):
     _TRAIN_PRETRAINING_HEADS = True
 
     def __init__(self, config=None, nlp_model_type: Optional[str] = None, kg_embedding_dict_path: Optional[str] = None,
@@ -141,10 +125,7 @@ class STonKGsForPreTraining(nn.Module):
         :param nlp_model_type: LOCAL directory of the LM backbone (config.json + pytorch_model.bin|model.safetensors)
         :param kg_embedding_dict_path: TSV of node2vec embeddings (prepare_df format)
         :param kg_embeddings: alternative to the TSV: [K, H] tensor in TSV row order (synthetic tables)"""
-        super().__init__()
-        if not torch.cuda.is_available():
-            raise hip.StonkHipError("STonKGsForPreTraining needs an MI355X: the hot path has no CPU fallback")
-        self._device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        super().__init__(device)
         if nlp_model_type is not None and os.path.isdir(nlp_model_type):
             cfg = STonKGsConfig.from_pretrained(nlp_model_type)
             if config is not None:  # keep run-time knobs (dropout) of an explicit config
@@ -189,8 +170,6 @@ class STonKGsForPreTraining(nn.Module):
         self.lm_sep_id, self.lm_mask_id, self.lm_unk_id = SEP_ID, MASK_ID, UNK_ID
         self.engine = Engine(cfg, self._store, self._bb_store, n_bb, dev)
         self.materialize_logits: Optional[bool] = None  # None = "only when not training"
-        self._segment_hook = None
-        self._anchor = torch.zeros((), device=dev, requires_grad=True)
         # ---- init weights, KG table
         self._init_weights(seed)
         if nlp_model_type is not None and os.path.isdir(nlp_model_type):
@@ -209,7 +188,7 @@ class STonKGsForPreTraining(nn.Module):
         names = names if names is not None else [f"node{r}" for r in range(K)] if K <= 4096 else None
         self.kg_idx_to_name = dict(zip(numeric_indices, names)) if names is not None else _LazyNames(numeric_indices)
         self._numeric_indices = torch.tensor(numeric_indices, device=dev)
-        self._grad_views = {n: p.grad for n, p in self.named_parameters() if p.requires_grad}
+        self._bind_grad_views()
         self.refresh()
 
     # -------------------------------------------------------------- construction helpers
@@ -217,21 +196,6 @@ class STonKGsForPreTraining(nn.Module):
     def _head_specs(cfg):
         """Extra trainable tensors a subclass puts in FRONT of the flat buffer (their gradients are final first)."""
         return []
-
-    def _init_weights(self, seed: int) -> None:
-        """BERT init (hf _init_weights: N(0, initializer_range) matrices/embeddings, zero bias, unit LayerNorm)."""
-        g = torch.Generator(device="cpu").manual_seed(seed)
-        std = self.config.initializer_range
-        with torch.no_grad():
-            for store in {id(x): x for x in (self._store, self._bb_store, self._heads_store)}.values():
-                for name, (off, shape, _) in store.index.items():
-                    v = store.view(name)
-                    if "LayerNorm.weight" in name:
-                        v.fill_(1.0)
-                    elif name.endswith(".bias") or "LayerNorm.bias" in name:
-                        v.zero_()
-                    else:
-                        v.copy_((torch.randn(shape, generator=g) * std).to(v.device))
 
     def refresh(self) -> None:
         """Recompute everything derived from the fp32 masters: bf16 mirrors, W^T copies, the entity table with its
@@ -249,105 +213,17 @@ class STonKGsForPreTraining(nn.Module):
         self.kg_backbone = KGBackbone(table)
         self._mark_synced()
 
-    # -------------------------------------------------------------- masters <-> derived copies
-    # The GEMMs read bf16 mirrors and bf16 W^T copies of the fp32 master weights; the fused optimizer refreshes them itself.
-    # Anything ELSE that writes the masters is noticed here as far as torch lets it be noticed:
-    #  * in-place writes THROUGH the parameters (a torch optimizer's step, `p.copy_` / `p.add_` under no_grad,
-    #    `load_state_dict`) bump the version counter the parameter views share with their flat buffer;
-    #  * an autograd-driven backward sets `_external_step_pending`: whoever called loss.backward() is about to step the
-    #    masters, possibly through `p.data` - which has a version counter of its OWN and is invisible above. The flag stays
-    #    set until a version change is seen (the ordinary optimizer) or `refresh()` is called: while it is set, every forward
-    #    re-derives the copies (0.5 ms), so a `.data`-writing optimizer is never read stale;
-    #  * a write through `p.data` that no backward preceded (weight surgery before eval / encode) CANNOT be seen:
-    #    call `model.refresh()` after it.
-    def _mark_synced(self, clear_pending: bool = True) -> None:
-        self._synced_versions = (self._store.data._version, self._bb_store.data._version,
-                                 self._heads_store.data._version)
-        if clear_pending:
-            self._external_step_pending = False
+    def _stores(self) -> tuple:
+        return self._store, self._bb_store, self._heads_store
 
-    def _sync_derived(self) -> None:
-        """Called at the top of every forward: bring the bf16 mirrors / W^T copies (and, if the frozen backbone was
-        written, the entity table's LM special rows) up to date with externally modified master weights."""
-        v = (self._store.data._version, self._bb_store.data._version, self._heads_store.data._version)
-        if v == self._synced_versions and not self._external_step_pending:
-            return
-        self._wait_params()
-        changed = v != self._synced_versions
-        if v[1] != self._synced_versions[1]:
+    def _rederive(self, written: list) -> None:
+        if any(s is self._bb_store for s in written):
             self.refresh()              # backbone changed: special vectors of the entity table too (quirk Q2)
         else:
-            self.engine.refresh_derived(bf16_mirror=True)
-            self._mark_synced(clear_pending=changed)   # (no version change yet: the external step may still come via .data)
+            super()._rederive(written)
 
-    def zero_grad(self, set_to_none: bool = True) -> None:
-        """nn.Module.zero_grad on the flat gradient buffer: the engine's backward ACCUMULATES into it (+= / atomics), so
-        dropping the `.grad` attributes alone would leave last step's gradients in place. The buffer is zeroed for both
-        values of `set_to_none`; with True the attributes are dropped as torch does and re-attached by the next backward."""
-        self._wait_params()
-        self._store.grad.zero_()
-        for p in self.parameters():
-            if p.requires_grad:
-                p.grad = None if set_to_none else p.grad
-        if not set_to_none:
-            self._reattach_grads(force=True)
-
-    def _prepare_grads_for_autograd(self) -> None:
-        """torch semantics for `loss.backward()`: a parameter whose `.grad` is None starts from zero (an optimizer's
-        zero_grad(set_to_none=True) only drops the attributes), one that still has its view accumulates."""
-        params = [(n, p) for n, p in nn.Module.named_parameters(self) if p.requires_grad]
-        dropped = [n for n, p in params if p.grad is None]
-        if not dropped:
-            return
-        if len(dropped) == len(params):
-            self._store.grad.zero_()
-        else:
-            for n in dropped:
-                self._grad_views[n].zero_()
-
-    # -------------------------------------------------------------- nn.Module plumbing
-    @property
-    def device(self) -> torch.device:
-        return self._device
-
-    def _apply(self, fn, recurse=True):
-        probe = fn(torch.zeros(1, device=self._device))
-        if probe.device != self._device or probe.dtype != torch.float32:
-            raise NotImplementedError("construct STonKGsForPreTraining on its target GPU; parameters are views of flat "
-                                      "HBM buffers and cannot be moved or cast")
-        return self
-
-    # Accessors order the caller's stream after an optimizer step still running on the optimizer stream
-    # (Engine.wait_params): whatever they hand out is final for work enqueued on the current stream.
-    def _wait_params(self) -> None:
-        eng = self.__dict__.get("engine")
-        if eng is not None:
-            eng.wait_params()
-
-    def state_dict(self, *args, **kwargs):
-        self._wait_params()
-        return super().state_dict(*args, **kwargs)
-
-    def named_parameters(self, *args, **kwargs):
-        self._wait_params()
-        return super().named_parameters(*args, **kwargs)
-
-    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False, _refresh: bool = True):
-        self._wait_params()
-        res = super().load_state_dict(state_dict, strict=strict)
-        if _refresh:
-            self.refresh()
-        return res
-
-    def _reattach_grads(self, force: bool = False) -> None:
-        for name, p in nn.Module.named_parameters(self):
-            if p.requires_grad and (force or p.grad is None):
-                p.grad = self._grad_views[name]
-
-    def named_grad_views(self) -> Dict[str, torch.Tensor]:
-        """name -> view into the flat gradient buffer (stable across zero_grad(set_to_none=True))."""
-        self._wait_params()
-        return self._grad_views
+    def _backward(self, gscale: float, on_segment_done) -> None:
+        self.engine.backward(gscale, on_segment_done)
 
     # -------------------------------------------------------------- loaders
     @classmethod
@@ -387,39 +263,17 @@ class STonKGsForPreTraining(nn.Module):
             raise FileNotFoundError("set STONKGS_PRETRAINED_DIR to a local copy of stonkgs/stonkgs-150k")
         return cls.from_pretrained(path, **kwargs)
 
-    def save_pretrained(self, path: str, safe_serialization: bool = False) -> None:
-        """HF layout: config.json + pytorch_model.bin, or model.safetensors with ``safe_serialization=True`` (what newer
-        HF versions write by default; `from_pretrained` reads either)."""
-        self.config.save_pretrained(path)
-        sd = {k: v.detach().cpu().contiguous() for k, v in self.state_dict().items()}
-        if safe_serialization:
-            from safetensors.torch import save_file
-
-            save_file(sd, os.path.join(path, "model.safetensors"), metadata={"format": "pt"})
-        else:
-            torch.save(sd, os.path.join(path, "pytorch_model.bin"))
-
     # -------------------------------------------------------------- forward
     def forward(self, input_ids=None, attention_mask=None, token_type_ids=None, masked_lm_labels=None,
                 ent_masked_lm_labels=None, next_sentence_labels=None, return_dict=None, head_mask=None):
         """ref:stonkgs_model.py:149-258. ``head_mask`` is accepted and ignored (quirk Q8)."""
         cfg = self.config
-        dev = self._device
         if input_ids is None:
             raise ValueError("input_ids is required")
         if getattr(cfg, "output_attentions", False):   # (set after construction: the constructor refuses it already)
             cfg.validate_for_hip()
-
-        def prep(t):
-            if t is None:
-                return None
-            t = torch.as_tensor(t)
-            if t.device != dev or t.dtype != torch.long or not t.is_contiguous():
-                t = t.to(device=dev, dtype=torch.long).contiguous()
-            return t
-
-        input_ids, attention_mask, token_type_ids = prep(input_ids), prep(attention_mask), prep(token_type_ids)
-        mlm, elm, nsp = prep(masked_lm_labels), prep(ent_masked_lm_labels), prep(next_sentence_labels)
+        input_ids, attention_mask, token_type_ids = (self._long(t) for t in (input_ids, attention_mask, token_type_ids))
+        mlm, elm, nsp = (self._long(t) for t in (masked_lm_labels, ent_masked_lm_labels, next_sentence_labels))
         if input_ids.dim() != 2 or input_ids.shape[1] != cfg.max_position_embeddings:
             raise ValueError(f"input_ids must be [B, {cfg.max_position_embeddings}] (text half | entity half)")
         have_labels = mlm is not None and elm is not None and nsp is not None
@@ -456,17 +310,7 @@ class STonKGsForPreTraining(nn.Module):
         only (embedding extraction does): the encoder runs on the rows that are live keys or position 0, its last layer on
         position 0 alone behind the QKV projection (Engine.unpad), and the first element returned is None."""
         cfg = self.config
-        dev = self._device
-
-        def prep(t):
-            if t is None:
-                return None
-            t = torch.as_tensor(t)
-            if t.device != dev or t.dtype != torch.long or not t.is_contiguous():
-                t = t.to(device=dev, dtype=torch.long).contiguous()
-            return t
-
-        input_ids, attention_mask, token_type_ids = prep(input_ids), prep(attention_mask), prep(token_type_ids)
+        input_ids, attention_mask, token_type_ids = (self._long(t) for t in (input_ids, attention_mask, token_type_ids))
         if input_ids.dim() != 2 or input_ids.shape[1] != cfg.max_position_embeddings:
             raise ValueError(f"input_ids must be [B, {cfg.max_position_embeddings}] (text half | entity half)")
         self._sync_derived()
@@ -510,7 +354,7 @@ class STonKGsForPreTraining(nn.Module):
         if not resolved:
             raise ValueError("no layer selected")
         resolved = tuple(sorted(resolved))
-        input_ids, attention_mask, token_type_ids = (self._prep_long(t) for t in (input_ids, attention_mask, token_type_ids))
+        input_ids, attention_mask, token_type_ids = (self._long(t) for t in (input_ids, attention_mask, token_type_ids))
         if input_ids.dim() != 2 or input_ids.shape[1] != S:
             raise ValueError(f"input_ids must be [B, {S}] (text half | entity half)")
         B = input_ids.shape[0]
@@ -573,10 +417,10 @@ class STonKGsForPreTraining(nn.Module):
         names = ("masked_lm_labels", "ent_masked_lm_labels", "next_sentence_labels")
         if labels is not None and set(labels) - set(names):
             raise ValueError(f"labels: unknown key(s) {sorted(set(labels) - set(names))}; expected a subset of {names}")
-        lab = {k: self._prep_long(v) for k, v in (labels or {}).items() if v is not None}
+        lab = {k: self._long(v) for k, v in (labels or {}).items() if v is not None}
         if not lab:
             raise ValueError(f"labels: give a dict with at least one of {names}")
-        input_ids, attention_mask, token_type_ids = (self._prep_long(t) for t in (input_ids, attention_mask, token_type_ids))
+        input_ids, attention_mask, token_type_ids = (self._long(t) for t in (input_ids, attention_mask, token_type_ids))
         gxi, gn, grad = self._attribution_buffers(input_ids, return_gradient, max_bytes)
         B, half = input_ids.shape[0], self.config.half_length
         for k, v in lab.items():
@@ -591,14 +435,6 @@ class STonKGsForPreTraining(nn.Module):
         return res
 
     # -------------------------------------------------------------- evaluation / masked prediction (no dense logits)
-    def _prep_long(self, t):
-        if t is None:
-            return None
-        t = torch.as_tensor(t)
-        if t.device != self._device or t.dtype != torch.long or not t.is_contiguous():
-            t = t.to(device=self._device, dtype=torch.long).contiguous()
-        return t
-
     def _evaluate(self, input_ids, attention_mask, token_type_ids, mlm, elm, nsp, k: int):
         """Engine.evaluate + the trim to the true label counts: one device-to-host copy (the two counts and the
         engine's error word) on top of the packed encoder's own wait for its row count."""
@@ -637,7 +473,7 @@ class STonKGsForPreTraining(nn.Module):
         `topk_logprobs` [n, k] (logit - logsumexp; non-increasing, ties by lower id) and `nll` [n] (logsumexp - the
         label's logit). Class ids are in the label space the decoders are trained against - for entities the
         PREPROCESSING ids 0..K-1 (quirk Q1), not rows of the entity table (`entity_names` maps them)."""
-        t = {key: self._prep_long(v) for key, v in inputs.items()}
+        t = {key: self._long(v) for key, v in inputs.items()}
         return self._evaluate(t["input_ids"], t.get("attention_mask"), t.get("token_type_ids"), t["masked_lm_labels"],
                               t["ent_masked_lm_labels"], t["next_sentence_labels"], k)
 
@@ -647,14 +483,14 @@ class STonKGsForPreTraining(nn.Module):
         wherever `input_ids == self.lm_mask_id`, in either half. Returns {"text": (batch_index, position, topk_ids,
         topk_logprobs), "ent": (...)} - `position` within the half, ids in the decoders' label space (see
         `evaluate_batch`, whose path this is: labels of 0 at the wanted positions, loss and rank dropped)."""
-        input_ids = self._prep_long(input_ids)
+        input_ids = self._long(input_ids)
         half = self.config.half_length
         want = input_ids == self.lm_mask_id if positions is None else torch.as_tensor(positions).to(self._device) != 0
         if want.shape != input_ids.shape:
             raise ValueError("positions must be a bool [B, S] like input_ids")
         lab = torch.where(want, 0, -100)
         nsp = torch.zeros(input_ids.shape[0], dtype=torch.long, device=self._device)
-        res = self._evaluate(input_ids, self._prep_long(attention_mask), self._prep_long(token_type_ids),
+        res = self._evaluate(input_ids, self._long(attention_mask), self._long(token_type_ids),
                              lab[:, :half].contiguous(), lab[:, half:].contiguous(), nsp, k)
         return {nm: tuple(res[nm][key] for key in ("batch_index", "position", "topk_ids", "topk_logprobs"))
                 for nm in ("text", "ent")}
@@ -673,9 +509,7 @@ class STonKGsForPreTraining(nn.Module):
         """forward + hand-written backward in one call: what ``Trainer.training_step`` does through
         ``loss = model(**inputs)[0]; loss.backward()`` (hf:trainer.py:1892-1963), minus the autograd graph and the
         host sync on ``dloss``. Gradients are accumulated into the flat buffer; returns the (detached) loss."""
-        dev = self._device
-        t = {k: (v if (torch.is_tensor(v) and v.device == dev and v.dtype == torch.long and v.is_contiguous())
-                 else torch.as_tensor(v).to(device=dev, dtype=torch.long).contiguous()) for k, v in inputs.items()}
+        t = {k: self._long(v) for k, v in inputs.items()}
         self._sync_derived()
         out = self.engine.forward(t["input_ids"], t.get("attention_mask"), t.get("token_type_ids"),
                                   t["masked_lm_labels"], t["ent_masked_lm_labels"], t["next_sentence_labels"],
@@ -686,38 +520,7 @@ class STonKGsForPreTraining(nn.Module):
         return loss
 
 
-@dataclass
-class SequenceClassifierOutput:
-    """hf:modeling_outputs.SequenceClassifierOutput as returned by ref:stonkgs_finetuning.py:340-345."""
-
-    loss: Optional[torch.Tensor] = None
-    logits: Optional[torch.Tensor] = None
-    hidden_states: Optional[tuple] = None
-    attentions: Optional[tuple] = None
-
-    def __getitem__(self, k):
-        if isinstance(k, str):
-            return getattr(self, k)
-        return tuple(v for v in (self.loss, self.logits, self.hidden_states, self.attentions) if v is not None)[k]
-
-
-class _ClsStepFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, anchor, model, loss):
-        ctx.model = model
-        return loss.clone()
-
-    @staticmethod
-    def backward(ctx, dloss):
-        model = ctx.model
-        model._prepare_grads_for_autograd()
-        model.engine.backward_cls(float(dloss), model._segment_hook)
-        model._reattach_grads()
-        model._external_step_pending = True
-        return None, None, None
-
-
-class STonKGsForSequenceClassification(STonKGsForPreTraining):
+class STonKGsForSequenceClassification(SequenceClassifierFront, STonKGsForPreTraining):
     """Fine-tuning model of BASELINE config 5 (relation-type etc. classification): mirror of
     ref:src/stonkgs/models/stonkgs_finetuning.py:237-346. Same frozen LM backbone + KG table front, same encoder,
     pooled [CLS] -> dropout -> Linear(hidden, num_labels) -> CrossEntropyLoss. Like the reference it inherits from the
@@ -736,19 +539,11 @@ class STonKGsForSequenceClassification(STonKGsForPreTraining):
         self.num_labels = self.config.num_labels
         self.dropout = nn.Dropout(self.config.hidden_dropout_prob)  # naming only; the engine applies it
         self.classifier = _linear(self._store, "classifier", True)
-        self._grad_views = {n: p.grad for n, p in self.named_parameters() if p.requires_grad}
+        self._bind_grad_views()
 
     @staticmethod
     def _head_specs(cfg):
         return [("classifier.weight", (cfg.num_labels, cfg.hidden_size), None), ("classifier.bias", (cfg.num_labels,), None)]
-
-    def _prep(self, t):
-        if t is None:
-            return None
-        t = torch.as_tensor(t)
-        if t.device != self._device or t.dtype != torch.long or not t.is_contiguous():
-            t = t.to(device=self._device, dtype=torch.long).contiguous()
-        return t
 
     def _labels_and_mode(self, labels):
         """ref:stonkgs_finetuning.py:316-338: infer `problem_type` once from num_labels and the label dtype, as the
@@ -769,7 +564,7 @@ class STonKGsForSequenceClassification(STonKGsForPreTraining):
                 pt = "multi_label_classification"
             self.config.problem_type = pt
         if pt == "single_label_classification":
-            return self._prep(lt.reshape(-1)), None
+            return self._long(lt.reshape(-1)), None
         if pt not in ("regression", "multi_label_classification"):
             raise ValueError(f"unknown problem_type {pt!r}")
         f = lt.to(device=self._device, dtype=torch.float32).contiguous()
@@ -783,21 +578,13 @@ class STonKGsForSequenceClassification(STonKGsForPreTraining):
 
     def forward(self, input_ids=None, attention_mask=None, token_type_ids=None, position_ids=None, head_mask=None,
                 inputs_embeds=None, labels=None, output_attentions=None, output_hidden_states=None, return_dict=None):
+        return self._classify(*self._cls_inputs(input_ids, attention_mask, token_type_ids, labels), return_dict)
+
+    def _cls_inputs(self, input_ids, attention_mask, token_type_ids, labels):
         if input_ids is None:
             raise ValueError("input_ids is required")
         lab, mode = self._labels_and_mode(labels)
-        ids, am, tt = self._prep(input_ids), self._prep(attention_mask), self._prep(token_type_ids)
-        training = self.training
-        self._sync_derived()
-        need_bwd = lab is not None and torch.is_grad_enabled() and training
-        out = self.engine.forward_cls(ids, am, tt, lab, self.num_labels, training, need_bwd, mode)
-        loss = None
-        if lab is not None:
-            loss = _ClsStepFunction.apply(self._anchor, self, out["loss"]) if need_bwd else out["loss"].clone()
-        logits = out["logits"].clone()
-        if not return_dict:
-            return ((loss,) + (logits,)) if loss is not None else (logits,)
-        return SequenceClassifierOutput(loss=loss, logits=logits, hidden_states=None, attentions=None)
+        return self._long(input_ids), self._long(attention_mask), self._long(token_type_ids), lab, mode
 
     @torch.no_grad()
     def input_attributions(self, input_ids, attention_mask=None, token_type_ids=None, target=None,
@@ -812,7 +599,7 @@ class STonKGsForSequenceClassification(STonKGsForPreTraining):
         saliency) and, with ``return_gradient``, ``gradient`` (fp32 [B, S, H]; allocated up front, refused beyond
         ``max_bytes``). Padded positions other than position 0 are read by nothing: their entries are exactly 0.
         Dropout is off in either module mode; see the pre-training class's method for what the call leaves alone."""
-        input_ids, attention_mask, token_type_ids = (self._prep(t) for t in (input_ids, attention_mask, token_type_ids))
+        input_ids, attention_mask, token_type_ids = (self._long(t) for t in (input_ids, attention_mask, token_type_ids))
         gxi, gn, grad = self._attribution_buffers(input_ids, return_gradient, max_bytes)
         B, C = input_ids.shape[0], self.num_labels
         if target is not None:
@@ -820,7 +607,7 @@ class STonKGsForSequenceClassification(STonKGsForPreTraining):
                 if target.dtype in (torch.float16, torch.bfloat16, torch.float32, torch.float64, torch.bool) or \
                         tuple(target.shape) != (B,):
                     raise ValueError(f"target must be None, an int, or an integer tensor of shape [{B}]")
-                target = self._prep(target)
+                target = self._long(target)
                 lo, hi = (int(v) for v in torch.stack([target.min(), target.max()]).tolist()) if B else (0, 0)
             else:
                 lo = hi = int(target)
@@ -835,16 +622,6 @@ class STonKGsForSequenceClassification(STonKGsForPreTraining):
         if return_gradient:
             res["gradient"] = grad
         return res
-
-    def forward_backward(self, inputs, gscale: float = 1.0, on_segment_done=None):
-        lab, mode = self._labels_and_mode(inputs.get("labels"))
-        self._sync_derived()
-        out = self.engine.forward_cls(self._prep(inputs["input_ids"]), self._prep(inputs.get("attention_mask")),
-                                      self._prep(inputs.get("token_type_ids")), lab, self.num_labels,
-                                      self.training, True, mode)
-        loss = out["loss"].clone()
-        self.engine.backward_cls(gscale, on_segment_done)
-        return loss
 
 
 class _LazyNames:
@@ -861,15 +638,3 @@ class _LazyNames:
 
     def __len__(self):
         return len(self._idx)
-
-
-def _load_weights_file(path: str) -> Optional[Dict[str, torch.Tensor]]:
-    st = os.path.join(path, "model.safetensors")
-    if os.path.exists(st):
-        from safetensors.torch import load_file
-
-        return load_file(st)
-    pb = os.path.join(path, "pytorch_model.bin")
-    if os.path.exists(pb):
-        return torch.load(pb, map_location="cpu", weights_only=True)
-    return None

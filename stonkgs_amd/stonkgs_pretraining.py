@@ -22,6 +22,7 @@ import torch
 
 from . import _hip as hip
 from .data import collate, synthetic_batch
+from .flat_model import _load_weights_file, as_long
 from .params import FlatStore
 
 
@@ -499,9 +500,7 @@ class Trainer:
         dev = self.model.device
         ints = ("input_ids", "attention_mask", "token_type_ids", "masked_lm_labels", "ent_masked_lm_labels",
                 "next_sentence_labels")   # (anything else - a classification head's labels - is the model's to interpret)
-        return {k: (v if (k not in ints or (torch.is_tensor(v) and v.device == dev and v.dtype == torch.long and
-                                            v.is_contiguous()))
-                    else torch.as_tensor(v).to(device=dev, dtype=torch.long).contiguous()) for k, v in batch.items()}
+        return {k: as_long(v, dev) if k in ints else v for k, v in batch.items()}
 
     def training_step(self, model, inputs: Dict[str, torch.Tensor], num_items_in_batch=None, *,
                       next_inputs: Optional[Dict] = None) -> torch.Tensor:
@@ -683,8 +682,6 @@ class Trainer:
         return d
 
     def load_checkpoint(self, d: str) -> None:
-        from .stonkgs_model import _load_weights_file
-
         self.model.load_state_dict(_load_weights_file(d), strict=False)
         self.optimizer.load_state_dict(torch.load(os.path.join(d, "optimizer.pt"), weights_only=True))
         with open(os.path.join(d, "trainer_state.json")) as fh:

@@ -113,6 +113,64 @@ def test_fused_trainer_and_external_optimizer_agree(hip):
     np.testing.assert_allclose(le, lf, atol=3e-3)
 
 
+def _tiny_case(kind):
+    """(constructor, batch) of one model class at the smallest shape the kernels accept; dropout 0, B = 3."""
+    from stonkgs_amd.config import STonKGsConfig
+    from stonkgs_amd.data import synthetic_batch
+    from stonkgs_amd.nlp_baseline_model import BertForSequenceClassification
+    from stonkgs_amd.stonkgs_model import STonKGsForPreTraining, STonKGsForSequenceClassification
+
+    dims = dict(vocab_size=512, kg_vocab_size=300, hidden_size=128, num_hidden_layers=2, num_attention_heads=2,
+                intermediate_size=128, max_position_embeddings=256, hidden_dropout_prob=0.0,
+                attention_probs_dropout_prob=0.0)
+    rows = torch.randn(300, 128, generator=torch.Generator().manual_seed(341), dtype=torch.float64) * 0.3
+    batch = synthetic_batch(3, 512, 300, 256, seed=340, min_text=16)
+    labels = torch.tensor([2, 0, 1])
+    if kind == "pretraining":
+        return lambda: STonKGsForPreTraining(STonKGsConfig(**dims), kg_embeddings=rows, seed=5), batch
+    batch = {k: batch[k] for k in ("input_ids", "attention_mask", "token_type_ids")}
+    batch["labels"] = labels
+    if kind == "classification":
+        return lambda: STonKGsForSequenceClassification(STonKGsConfig(**dims, num_labels=3), kg_embeddings=rows, seed=5), batch
+    batch["input_ids"] = batch["input_ids"][:, :128] * batch["attention_mask"][:, :128]   # the text half alone: L = 128 < S
+    batch["attention_mask"], batch["token_type_ids"] = batch["attention_mask"][:, :128], batch["token_type_ids"][:, :128]
+    return lambda: BertForSequenceClassification(STonKGsConfig(**dims), num_labels=3, seed=5), batch
+
+
+@pytest.mark.parametrize("kind", ["pretraining", "classification", "text"])
+def test_autograd_bridge_and_forward_backward_leave_the_same_gradients(hip, kind):
+    """One bridge under the three classes: `loss = model(**batch)[0]; loss.backward()` and `forward_backward` on a twin
+    built from the same seed leave the same gradients (compared as `test_fused_trainer_and_external_optimizer_agree`
+    compares the two paths' losses: allclose, atol 3e-3), and only the autograd path announces an external step."""
+    make, batch = _tiny_case(kind)
+    ext, fused = make(), make()
+    ext.train()
+    fused.train()
+    for a, b in zip(ext.state_dict().values(), fused.state_dict().values()):
+        assert torch.equal(a, b)
+    assert not ext._external_step_pending and not fused._external_step_pending
+    loss = ext(**batch)[0]
+    assert not ext._external_step_pending
+    loss.backward()
+    assert ext._external_step_pending
+    lf = fused.forward_backward(batch)
+    assert not fused._external_step_pending
+    ext.engine.check_errors()
+    fused.engine.check_errors()
+    loss = loss.detach()
+    ge, gf = ext.named_grad_views(), fused.named_grad_views()
+    assert list(ge) == list(gf) == [n for n, p in ext.named_parameters() if p.requires_grad]
+    worst = max((float((ge[k] - gf[k]).abs().max()), k) for k in ge)
+    print(kind, "loss", float(loss), float(lf), "worst gradient difference", worst,
+          "largest gradient entry", max(float(g.abs().max()) for g in gf.values()))
+    np.testing.assert_allclose(float(loss), float(lf), atol=3e-3)
+    assert max(float(g.abs().max()) for g in gf.values()) > 0
+    params = dict(ext.named_parameters())
+    for k in ge:
+        assert params[k].grad is ge[k], k
+        np.testing.assert_allclose(ge[k].cpu().numpy(), gf[k].cpu().numpy(), atol=3e-3, err_msg=k)
+
+
 def test_hf_trainer_two_steps(hip, tmp_path):
     """The real `transformers.Trainer` (as ref:stonkgs_pretraining.py:215-223 builds it: model, TrainingArguments, dataset)
     for two optimizer steps against the fused Trainer on the same batches."""
