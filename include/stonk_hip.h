@@ -122,7 +122,9 @@ int stonk_text_embed_ln_fwd(const int64_t* input_ids, int64_t ld_ids, const floa
                             void* stream);
 
 /* d(position_embeddings) and d(token_type_embeddings) from d(embedding sum) (bf16 [B*S,H]); accumulates.
- * row_of_pos (nullable): packed layout - dx row of padded position p is row_of_pos[p], -1 = dropped (no gradient). */
+ * row_of_pos (nullable): packed layout - dx row of padded position p is row_of_pos[p], -1 = dropped (no gradient).
+ * token_type_ids (nullable: every position is type 0). type_rows is 1 or 2 - with 1, row 1 of dtype is not touched; more
+ * type rows are refused (STONK_ESHAPE): the kernel keeps sums for rows 0 and 1 only. H % 8 == 0, H <= 1024. */
 int stonk_embed_grad(const void* dx, const int64_t* token_type_ids, float* dpos, float* dtype, int B, int S, int H,
                      int type_rows, const int* row_of_pos, void* stream);
 
@@ -267,7 +269,9 @@ int stonk_scatter_rows_f32_to_bf16(const float* src, int64_t ld_src, const int* 
 
 /* Per labelled row: loss_sum += logsumexp(logits[row,:ncols]) - logits[row,target];
  * dlogits (bf16, nullable, cap_rows rows allocated) = (softmax - onehot) * grad_scale / count, rows
- * [count, roundup64(count)) zeroed. Bit 3 of *err_flag: target out of range. */
+ * [count, roundup64(count)) zeroed. Bit 3 of *err_flag: target out of range. The sum is built in a fixed order (one share
+ * per workgroup, added in double by the last workgroup to finish, then ONE addition to *loss_sum): the same bits on every
+ * launch. The shares live in the library (16 sets used in turn): at most 16 of these launches may be in flight at once. */
 int stonk_softmax_xent_fwd_bwd(const float* logits, int64_t ld, int ncols, int npad, const int* targets,
                                const int* count_dev, float* loss_sum, void* dlogits, int64_t ld_d, float grad_scale,
                                int cap_rows, int* err_flag, void* stream);

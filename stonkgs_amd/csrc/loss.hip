@@ -6,6 +6,7 @@
 // ref:src/stonkgs/models/stonkgs_model.py:223-245. Only rows whose label is not -100 contribute to the
 // loss or to any gradient, so the decoders run on the compacted labelled rows (identical loss and
 // gradients, SURVEY.md section 8d "label-sparse"); the row count lives in device memory - no host sync.
+#include <atomic>
 #include "common.h"
 #include "stonk_flags.h"
 
@@ -130,10 +131,21 @@ __global__ __launch_bounds__(256) void scatter_rows_f32_kernel(const float* __re
 
 // One block per labelled row: online (max, sum-exp) sweep of the logits (fp32, or the fp16 the decoder GEMM can leave:
 // LT), then a second sweep writes dlogits = (softmax - onehot) * gscale / count as bf16 (columns [ncols, npad) = 0).
-// loss_sum += lse - x[target]. All arithmetic in fp32. HBM-bound: 10 bytes per logit with fp32 logits, 6 with fp16.
+// loss_sum += sum of (lse - x[target]). All arithmetic in fp32 (the last sum, over the workgroups' shares, in double). HBM-bound: 10 bytes per logit with fp32 logits, 6 with fp16.
 #ifndef STONK_XENT_BLOCKS
 #define STONK_XENT_BLOCKS 2048   // workgroups, one labelled row at a time each; alone at 2 432 rows x 175 104 (tools/bench_xent.py, us): 256: 942, 512: 714, 1024: 547, 2048: 529
 #endif
+// The loss of the labelled rows is summed in a FIXED order: a workgroup keeps the sum of its own rows, leaves it in a slot, and
+// the last workgroup to finish (ticket) adds the STONK_XENT_BLOCKS slots in double precision and adds the total to
+// *loss_sum once. (One fp32 atomicAdd per row - some 2000 terms onto one running sum in arrival order - was good to 1e-6 of
+// the sum and differed from launch to launch.) Slots and ticket are the library's: XENT_POOL sets of them, zero at load,
+// taken in turn by the launchers, the ticket left at zero by the kernel - so launches in flight on different streams do
+// not meet unless more than XENT_POOL of them overlap; a training step has two (the text and the entity decoder).
+constexpr int XENT_POOL = 16;
+__device__ float g_xent_part[XENT_POOL][STONK_XENT_BLOCKS];
+__device__ unsigned g_xent_ticket[XENT_POOL];
+std::atomic<unsigned> g_xent_next{0};
+
 template <typename LT> struct LogitVec;
 template <> struct LogitVec<float> {
   static __device__ __forceinline__ void load8(const float* x, float (&v)[8]) {
@@ -155,8 +167,9 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(const LT* __restrict_
                                                            const int* __restrict__ targets, const int* __restrict__ count,
                                                            float* __restrict__ loss_sum, bf16* __restrict__ dlogits,
                                                            long ld_d, float gscale, int* __restrict__ err,
-                                                           int cap_rows) {
+                                                           int cap_rows, int slot) {
   __shared__ float red_m[4], red_s[4];
+  float own_loss = 0.f;   // (thread 0) sum over this workgroup's rows
   const int cnt = *count;
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
   const float g = gscale / (float)cnt;
@@ -224,7 +237,7 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(const LT* __restrict_
       if (t == 0) atomicOr(err, 8);
       tgt = 0;
     }
-    if (t == 0) atomicAdd(loss_sum, lse - (float)x[tgt]);
+    if (t == 0) own_loss += lse - (float)x[tgt];
     if (dlogits) {
       bf16* d = dlogits + (long)row * ld_d;
       const int p8 = npad >> 3, f8 = ncols >> 3;   // whole pieces of the row: [0, f8); [f8, p8) holds the row's end and the padding
@@ -282,6 +295,34 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(const LT* __restrict_
       for (int j = 0; j < 8; ++j) z[j] = (bf16)0.f;
       for (int i = t; i < (npad >> 3); i += 256) *(bf16x8*)(d + i * 8) = z;
     }
+  }
+  float* part = g_xent_part[slot];
+  unsigned* ticket = &g_xent_ticket[slot];
+  __shared__ bool last;
+  __shared__ double wide[256];
+  if (t == 0) {
+    // No release fence here: at agent scope it writes back every dirty line of this XCD's L2 - the dlogits just stored -
+    // once per workgroup (0.25 ms per launch at the benchmark shape). The share needs none: it is written by an agent-scope
+    // atomic WITH return, whose value has come back (vmcnt 0) before the ticket is taken, and the last workgroup reads the
+    // slots with agent-scope atomic loads.
+    (void)__hip_atomic_exchange(&part[blockIdx.x], own_loss, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
+  }
+  __syncthreads();
+  if (!last) return;
+  double tot = 0.0;   // strided slots, then a fixed tree: the same order on every launch
+  for (int i = t; i < (int)gridDim.x; i += 256)
+    tot += (double)__hip_atomic_load(&part[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  wide[t] = tot;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (t < o) wide[t] += wide[t + o];
+    __syncthreads();
+  }
+  if (t == 0) {
+    if (cnt > 0) atomicAdd(loss_sum, (float)wide[0]);
+    __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
   }
 }
 
@@ -374,7 +415,8 @@ extern "C" int stonk_softmax_xent_fwd_bwd(const float* logits, int64_t ld, int n
   STONK_CHECK_ARG(ncols > 0 && npad >= ncols && npad % 8 == 0 && ld >= npad && ld % 4 == 0, STONK_ESHAPE);
   STONK_CHECK_ARG(!dlogits || (ld_d >= npad && ld_d % 8 == 0), STONK_ESHAPE);
   hipLaunchKernelGGL(softmax_xent_kernel<float>, dim3(STONK_XENT_BLOCKS), dim3(256), 0, (hipStream_t)stream, logits, (long)ld, ncols,
-                     npad, targets, count_dev, loss_sum, (bf16*)dlogits, (long)ld_d, grad_scale, err_flag, cap_rows);
+                     npad, targets, count_dev, loss_sum, (bf16*)dlogits, (long)ld_d, grad_scale, err_flag, cap_rows,
+                     (int)(g_xent_next.fetch_add(1) % XENT_POOL));
   return stonk_launch_status();
 }
 
@@ -387,7 +429,8 @@ extern "C" int stonk_softmax_xent_f16_fwd_bwd(const void* logits_f16, int64_t ld
   STONK_CHECK_ARG((uintptr_t)logits_f16 % 16 == 0, STONK_EALIGN);
   hipLaunchKernelGGL(softmax_xent_kernel<_Float16>, dim3(STONK_XENT_BLOCKS), dim3(256), 0, (hipStream_t)stream,
                      (const _Float16*)logits_f16, (long)ld, ncols, npad, targets, count_dev, loss_sum, (bf16*)dlogits,
-                     (long)ld_d, grad_scale, err_flag, cap_rows);
+                     (long)ld_d, grad_scale, err_flag, cap_rows,
+                     (int)(g_xent_next.fetch_add(1) % XENT_POOL));
   return stonk_launch_status();
 }
 

@@ -838,7 +838,8 @@ extern "C" int stonk_text_embed_ln_fwd(const int64_t* input_ids, int64_t ld_ids,
 extern "C" int stonk_embed_grad(const void* dx, const int64_t* token_type_ids, float* dpos, float* dtype, int B, int S,
                                 int H, int type_rows, const int* row_of_pos, void* stream) {
   STONK_CHECK_ARG(dx && dpos && dtype, STONK_EINVAL);
-  STONK_CHECK_ARG(B >= 0 && S > 0 && H > 0 && H % 8 == 0 && H <= 1024 && type_rows >= 1, STONK_ESHAPE);
+  // (the kernel keeps sums for type rows 0 and 1 only: a third row would silently get no gradient)
+  STONK_CHECK_ARG(B >= 0 && S > 0 && H > 0 && H % 8 == 0 && H <= 1024 && type_rows >= 1 && type_rows <= 2, STONK_ESHAPE);
   STONK_CHECK_ARG((uintptr_t)dx % 16 == 0, STONK_EALIGN);
   if (B == 0) return STONK_OK;
   hipLaunchKernelGGL(embed_grad_kernel, dim3(S), dim3((H >> 3) * EG), 0, (hipStream_t)stream, (const bf16*)dx,

@@ -33,6 +33,8 @@ __global__ __launch_bounds__(256) void small_linear_fwd_kernel(const void* __res
   }
 }
 
+constexpr int WG_MC = 64;   // rows per piece of the weight-gradient sums (both kernels)
+
 // dpre = dy * (1 - y^2) for tanh, else dy.
 // dW[n][k] += sum_m dpre[m][n] x[m][k];  db[n] += sum_m dpre[m][n]     (one thread per (n, k))
 __global__ __launch_bounds__(256) void small_linear_wgrad_kernel(const float* __restrict__ dy, const float* __restrict__ y,
@@ -42,15 +44,23 @@ __global__ __launch_bounds__(256) void small_linear_wgrad_kernel(const float* __
   const bool xf32 = act & STONK_SMALL_X_F32, th = act & STONK_SMALL_TANH;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < (long)N * K; i += (long)gridDim.x * 256) {
     const int n = (int)(i / K), k = (int)(i - (long)n * K);
+    // rows are summed WG_MC at a time and the pieces then added, so a term meets a partial sum of 64 terms, not of
+    // thousands: one running fp32 sum over 1537 rows of dy ~ N(0, 1) was 7.4e-5 off in a db of 59, this order 8e-6
     float acc = 0.f, accb = 0.f;
-    for (int m = 0; m < M; ++m) {
-      float d = dy[(long)m * N + n];
-      if (th) {
-        const float yy = y[(long)m * N + n];
-        d *= 1.f - yy * yy;
+    for (int m0 = 0; m0 < M; m0 += WG_MC) {
+      const int m1 = m0 + WG_MC < M ? m0 + WG_MC : M;
+      float a = 0.f, ab = 0.f;
+      for (int m = m0; m < m1; ++m) {
+        float d = dy[(long)m * N + n];
+        if (th) {
+          const float yy = y[(long)m * N + n];
+          d *= 1.f - yy * yy;
+        }
+        a += d * load_x(x, (long)m * ldx + k, xf32);
+        ab += d;
       }
-      acc += d * load_x(x, (long)m * ldx + k, xf32);
-      accb += d;
+      acc += a;
+      accb += ab;
     }
     dW[i] += acc;
     if (k == 0 && db) db[n] += accb;
@@ -86,10 +96,18 @@ __global__ __launch_bounds__(256) void small_linear_wgrad_tiled_kernel(const flo
     float acc[WG_NT];
 #pragma unroll
     for (int j = 0; j < WG_NT; ++j) acc[j] = 0.f;
-    for (int m = 0; m < M; ++m) {
-      const float xv = load_x(x, (long)m * ldx + k, xf32);
+    for (int m0 = 0; m0 < M; m0 += WG_MC) {   // (pieces of WG_MC rows, as in the untiled kernel; one piece at the pooler's M = 64)
+      const int m1 = m0 + WG_MC < M ? m0 + WG_MC : M;
+      float a[WG_NT];
 #pragma unroll
-      for (int j = 0; j < WG_NT; ++j) acc[j] += dpre_t[m * WG_NT + j] * xv;
+      for (int j = 0; j < WG_NT; ++j) a[j] = 0.f;
+      for (int m = m0; m < m1; ++m) {
+        const float xv = load_x(x, (long)m * ldx + k, xf32);
+#pragma unroll
+        for (int j = 0; j < WG_NT; ++j) a[j] += dpre_t[m * WG_NT + j] * xv;
+      }
+#pragma unroll
+      for (int j = 0; j < WG_NT; ++j) acc[j] += a[j];
     }
 #pragma unroll
     for (int j = 0; j < WG_NT; ++j)
@@ -97,7 +115,12 @@ __global__ __launch_bounds__(256) void small_linear_wgrad_tiled_kernel(const flo
   }
   if (blockIdx.x == 0 && threadIdx.x < WG_NT && n0 + threadIdx.x < N && db) {
     float s = 0.f;
-    for (int m = 0; m < M; ++m) s += dpre_t[m * WG_NT + threadIdx.x];
+    for (int m0 = 0; m0 < M; m0 += WG_MC) {
+      const int m1 = m0 + WG_MC < M ? m0 + WG_MC : M;
+      float a = 0.f;
+      for (int m = m0; m < m1; ++m) a += dpre_t[m * WG_NT + threadIdx.x];
+      s += a;
+    }
     db[n0 + threadIdx.x] += s;
   }
 }
@@ -222,7 +245,7 @@ __global__ __launch_bounds__(256) void elementwise_loss_kernel(const float* __re
                                                                int B, int C, int mode, float* __restrict__ loss_out,
                                                                float* __restrict__ dx, float gscale) {
   __shared__ float red[4];
-  __shared__ float s_mean_y, s_mean_y2;
+  __shared__ float s_mean_y, s_res_y, s_var_y;
   const int n = B * C;
   auto block_sum = [&](float v) {
     v = wave_sum(v);
@@ -232,16 +255,29 @@ __global__ __launch_bounds__(256) void elementwise_loss_kernel(const float* __re
     return (red[0] + red[1]) + (red[2] + red[3]);
   };
   if (mode == STONK_LOSS_MSE_BROADCAST) {
-    float sy = 0.f, sy2 = 0.f;
-    for (int j = threadIdx.x; j < B; j += 256) {
-      sy += y[j];
-      sy2 += y[j] * y[j];
-    }
+    // mean_j (x_i - y_j)^2 = (x_i - mean y)^2 + var y, from two passes over y: m = the fp32 mean, then the sums of
+    // (y_j - m) and (y_j - m)^2. The expanded form x^2 - 2 x mean(y) + mean(y^2) cancels in fp32 once |x|, |y| are large
+    // against their spread (relative error of the loss 2e-2 at x, y ~ 50 +- 0.1). m itself is off the mean by up to half
+    // an ulp of |y| - at 50 that is still 6e-6 of the loss and 2e-5 of the gradient - so the residual r = mean_j (y_j - m),
+    // which the second pass gets from small exact differences, is carried along: mean y = m + r, var y = mean (y - m)^2 - r^2
+    float sy = 0.f;
+    for (int j = threadIdx.x; j < B; j += 256) sy += y[j];
     sy = block_sum(sy);
-    sy2 = block_sum(sy2);
+    if (threadIdx.x == 0) s_mean_y = sy / (float)B;
+    __syncthreads();
+    const float my = s_mean_y;
+    float sr = 0.f, sv = 0.f;
+    for (int j = threadIdx.x; j < B; j += 256) {
+      const float d = y[j] - my;
+      sr += d;
+      sv += d * d;
+    }
+    sr = block_sum(sr);
+    sv = block_sum(sv);
     if (threadIdx.x == 0) {
-      s_mean_y = sy / (float)B;
-      s_mean_y2 = sy2 / (float)B;
+      const float r = sr / (float)B;
+      s_res_y = r;
+      s_var_y = sv / (float)B - r * r;
     }
     __syncthreads();
   }
@@ -254,8 +290,9 @@ __global__ __launch_bounds__(256) void elementwise_loss_kernel(const float* __re
       l = d * d;
       g = 2.f * d;
     } else if (mode == STONK_LOSS_MSE_BROADCAST) {
-      l = xi * xi - 2.f * xi * s_mean_y + s_mean_y2;   // mean_j (x_i - y_j)^2
-      g = 2.f * (xi - s_mean_y);
+      const float d = (xi - s_mean_y) - s_res_y;
+      l = d * d + s_var_y;   // mean_j (x_i - y_j)^2
+      g = 2.f * d;
     } else {
       const float yi = y[i];
       const float e = __expf(-fabsf(xi));
