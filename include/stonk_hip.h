@@ -183,6 +183,11 @@ int stonk_unpad_plan(const int64_t* attention_mask, const int64_t* text_labels, 
 /* Fused attention, head_dim 64, S % 128 == 0, S <= 4096: out = dropout(softmax(q k^T * scale + mask)) v.
  * q/k/v: column slices of the [T, 3H] projection (row stride ld), head h at columns h*64..; attention_mask int64
  * [B,S] (0 = masked key) or NULL; lse fp32 [B,NH,S]. Replaces hf:modeling_bert.py:188-203 (eager :111-136).
+ * A masked key has probability exactly 0 and gets exactly zero dk / dv - unless NO key of a sequence is unmasked: the
+ * sequence then attends uniformly over its own rows, P = 1/n with n = S (padded) or the sequence's length (packed), as
+ * the eager path does once finfo.min has absorbed every score; forward and backward agree on that at every S, dq / dk /
+ * dv are those of the formulas with that P, and the sequence's lse entries are finite, about -2^100 * scale, and
+ * meaningless.
  * PACKED layout (seq_offsets != NULL, int32 [B+1], device): sequence b is rows seq_offsets[b] .. seq_offsets[b+1]-1 of
  * q/k/v/out (any length <= S, no alignment), attention_mask is then REQUIRED and holds one word per packed ROW; lse (and
  * delta_ws) keep the [B,NH,S] layout. What the trainable encoder runs on once the rows that nothing reads - padding that

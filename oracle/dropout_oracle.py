@@ -10,8 +10,20 @@ kernel must have dropped instead of reading that off the kernel's own output.
     keep iff z >= thr32(p)
 
 Covered: the element form (``stonk_keep``) used by the LayerNorm kernels, the embedding front-ends (row = the output row, in
-the packed layout the packed row) and ``stonk_dropout_f32`` (row 0, column = the flat element index). The 4 x 4 block form of
-the attention probabilities is not restated here.
+the packed layout the packed row) and ``stonk_dropout_f32`` (row 0, column = the flat element index).
+
+The attention probabilities use the 4 x 4 BLOCK form (``stonk_blk_round1`` / ``stonk_blk_keep``): one first round per block of
+four query rows x four keys, one last round per element with one of sixteen multipliers (``keep_block``):
+
+    rk = (row >> 2) * G_ROW + seed_mix(seed)                        (mod 2^32)
+    ck = (key >> 2) * G_COL                                         (mod 2^32)
+    x  = rk ^ ck
+    y8 = (lo24(x) * C1 + x  mod 2^32) >> 8
+    z  = y8 * C2_BLK[4 * (row & 3) + (key & 3)]                     (mod 2^32)
+    keep iff z >= thr32(p)
+
+with row = (b * NH + h) * S + q, q the query's row INSIDE its sequence and S the launch's ``S`` argument (in the packed
+layout too), and key = the key's row inside its sequence (``attention_keep``).
 """
 from __future__ import annotations
 
@@ -23,6 +35,9 @@ G_ROW = np.uint64(0x9E3779B1)
 G_COL = np.uint64(0x85EBCA77)
 C1 = np.uint64(0xB5297B)
 C2 = np.uint64(0x68E31D)
+# STONK_C2_BLK: the last-round multiplier of block member 4 * (row & 3) + (key & 3)
+C2_BLK = np.array([0x45821F, 0xFAC0C5, 0xD90A1B, 0xE6B85B, 0xE11EE7, 0x6E41B9, 0xB8115D, 0xB1494B,
+                   0xBF440F, 0xA96C25, 0x7B570F, 0xA2609D, 0x98207D, 0xB5677D, 0x82C471, 0xAC3C19], dtype=np.uint64)
 
 
 def _hash32(x: np.uint64) -> np.uint64:
@@ -62,3 +77,23 @@ def keep(rows, cols, seed: int, p: float) -> np.ndarray:
 def keep_flat(n: int, seed: int, p: float) -> np.ndarray:
     """Keep mask bool[n] of ``stonk_dropout_f32``: row 0, column = element index."""
     return keep([0], np.arange(n), seed, p)[0]
+
+
+def keep_block(rows, keys, seed: int, p: float) -> np.ndarray:
+    """Keep mask bool[len(rows), len(keys)] of the 4 x 4 block form: element (i, j) is that of row rows[i] and key keys[j]."""
+    r = np.asarray(rows, dtype=np.int64).reshape(-1, 1).astype(np.uint64) & _M32
+    k = np.asarray(keys, dtype=np.int64).reshape(1, -1).astype(np.uint64) & _M32
+    two, three = np.uint64(2), np.uint64(3)
+    rk = ((r >> two) * G_ROW + np.uint64(seed_mix(seed))) & _M32
+    ck = ((k >> two) * G_COL) & _M32
+    x = rk ^ ck
+    y8 = (((x & _M24) * C1 + x) & _M32) >> np.uint64(8)
+    c2 = C2_BLK[(np.uint64(4) * (r & three) + (k & three)).astype(np.int64)]
+    z = (y8 * c2) & _M32
+    return z >= np.uint64(thr32(p))
+
+
+def attention_keep(b: int, h: int, NH: int, S: int, n_queries: int, n_keys: int, seed: int, p: float) -> np.ndarray:
+    """Keep mask bool[n_queries, n_keys] of head h of sequence b in a launch with `NH` heads and the argument `S`:
+    the first n_queries query rows of the sequence against its first n_keys keys."""
+    return keep_block((b * NH + h) * S + np.arange(n_queries), np.arange(n_keys), seed, p)

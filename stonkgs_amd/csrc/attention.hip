@@ -29,6 +29,10 @@ constexpr float LN2 = 0.6931471805599453f;
 // products are absorbed (every masked score is exactly NEG_MASK, as the reference's finfo.min absorbs them) and
 // NEG_MASK * scale is exact, so exp2(fma(s, scale, -max)) is exactly 1 for a row whose keys are all masked.
 constexpr float NEG_MASK = -0x1p100f;
+// Keys past the end of a packed sequence (the rest of its last 64-key tile: their K rows arrive as zeros) sit strictly
+// BELOW the masked ones: when every real key is masked, the row maximum is NEG_MASK and the real keys' exp2 is 1 - theirs
+// must still be 0, or a sequence of n rows would attend uniformly over 64 ceil(n / 64) keys.
+constexpr float NEG_PAST = -0x1p101f;
 constexpr float NEG_INIT = -0x1p120f;
 
 // The block multipliers of one row (four consecutive entries of STONK_C2_BLK) or of one column (every fourth), selected
@@ -278,8 +282,9 @@ __device__ __forceinline__ AttnBlock attn_block() {
 // tile loop walk the set bits only - in the STonKGs layout the padding of the text half, 112 of 512 positions on average
 // in the benchmark's batches. In two halves, so that the mask words travel while the kernel's other first loads do (asked
 // for first, they are also the first to arrive): live_issue() requests them, live_finish() returns the bits - 0 when NO
-// key of the sequence is unmasked (the reference then attends uniformly: the callers walk every tile), all ones without a
-// mask or beyond 1024 keys. live_finish() contains two barriers.
+// key of the sequence is unmasked (the reference then attends uniformly over the sequence's own rows: the callers walk every
+// tile), all ones without a mask; beyond 1024 keys all ones or 0 (the words are read in a loop there, for that one bit).
+// live_finish() contains two barriers (one beyond 1024 keys).
 struct LiveTiles {
   long mv[4];
 };
@@ -292,7 +297,7 @@ __device__ __forceinline__ void live_issue(LiveTiles& t, const long* mask, long 
     t.mv[c] = key < S ? mask[tok0 + key] : 0;   // (S: the rows of THIS sequence)
   }
 }
-// With `kbias` (forward, dQ): the additive bias of EVERY key of the sequence (0, or NEG_MASK for a masked key and for the
+// With `kbias` (forward, dQ): the additive bias of EVERY key of the sequence (0, NEG_MASK for a masked key, NEG_PAST for the
 // keys past the sequence's end) goes to LDS here, once - the tile loop reads it from there instead of loading and
 // converting a tile's 64 mask words with every tile (a load per tile whose 64-bit word also cost the forward kernel
 // the two registers that pushed it into scratch).
@@ -302,12 +307,14 @@ __device__ __forceinline__ uint64_t live_finish(const LiveTiles& t, const long* 
   const int nt = (n + TK - 1) / TK;
   const uint64_t all = nt >= 64 ? ~0ull : ((1ull << nt) - 1);
   if (!HAS_MASK) return all;
-  if (S > 1024) {   // (no tile skipping beyond 1024 keys: the words are only turned into the bias)
-    if (kbias) {
-      for (int key = tid; key < S; key += 256) kbias[key] = (key < n && mask[tok0 + key] != 0) ? 0.f : NEG_MASK;
-      __syncthreads();
+  if (S > 1024) {   // (no tile skipping beyond 1024 keys: the words become the bias and ONE bit, "some key is unmasked")
+    int any = 0;
+    for (int key = tid; key < S; key += 256) {
+      const bool live = key < n && mask[tok0 + key] != 0;
+      any |= live;
+      if (kbias) kbias[key] = live ? 0.f : (key < n ? NEG_MASK : NEG_PAST);
     }
-    return all;
+    return __syncthreads_or(any) ? all : 0;
   }
   __shared__ int tile_live[16];
   const int lane = tid & 63, wave = tid >> 6;
@@ -315,7 +322,7 @@ __device__ __forceinline__ uint64_t live_finish(const LiveTiles& t, const long* 
   for (int c = 0; c < 4; ++c) {
     const uint64_t b = __ballot(t.mv[c] != 0);
     if (lane == 0) tile_live[c * 4 + wave] = b != 0;
-    if (kbias && c * 256 + tid < S) kbias[c * 256 + tid] = t.mv[c] != 0 ? 0.f : NEG_MASK;
+    if (kbias && c * 256 + tid < S) kbias[c * 256 + tid] = t.mv[c] != 0 ? 0.f : (c * 256 + tid < n ? NEG_MASK : NEG_PAST);
   }
   __syncthreads();
   const uint64_t m = __ballot(lane < nt && tile_live[lane & 15] != 0);
@@ -484,14 +491,16 @@ __global__ __launch_bounds__(128) void attn_delta_kernel(const AttnArgs p) {
   if (q >= nq) return;
   const bf16* drow = p.dout + (tok0 + q) * p.lddo + h * HD;
   const bf16* orow = p.out + (tok0 + q) * p.ldo + h * HD;
-  float dlt = 0.f;
+  // In the dQ kernel's order - its lane pair (r, hh) sums the 8-column chunks 2 st + hh, st = 0..3, then adds the two
+  // halves - so that the dK/dV kernel reads bitwise the same delta from either and the phases equal the single call.
+  float half[2] = {0.f, 0.f};
 #pragma unroll
   for (int c = 0; c < 8; ++c) {
     const bf16x8 d = *(const bf16x8*)(drow + 8 * c), o = *(const bf16x8*)(orow + 8 * c);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) dlt += (float)o[j] * (float)d[j];
+    for (int j = 0; j < 8; ++j) half[c & 1] += (float)o[j] * (float)d[j];
   }
-  p.delta[(long)(b * p.NH + h) * S + q] = dlt;
+  p.delta[(long)(b * p.NH + h) * S + q] = half[0] + half[1];
 }
 
 // ------------------------------------------------------------------ backward: dQ (query on the lane)

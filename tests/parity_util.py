@@ -1,4 +1,5 @@
-"""Tolerances of the fp64 parity tests (test_rowwise_parity_gpu.py, test_head_parity_gpu.py).
+"""Tolerances of the fp64 parity tests (test_rowwise_parity_gpu.py, test_head_parity_gpu.py; the attention kernels' file,
+test_attention_parity_gpu.py, takes its absolute term A from tol_a and adds a per-element bound: tests/attention_ref.py).
 
 Every comparison is  kernel output  against  r = the operation in float64 on the CPU, from the same bf16 / fp32 inputs.
 The absolute term A of a tolerance comes from the REFERENCE alone: the same operation by torch's own float32 op on the CPU
