@@ -215,6 +215,43 @@ int stonk_attention_bwd_phases(int phases, const void* q, const void* k, const v
                                void* dk, int64_t ldd, void* dv, int B, int NH, int S, int D, float scale, float drop_p,
                                uint32_t seed, void* stream);
 
+/* Block-sparse (BigBird) attention, head_dim 64, block size 64, padded layout only, no dropout (csrc/bigbird_attention.hip).
+ * Replaces hf:models/big_bird/modeling_big_bird.py:295-744 (BigBirdBlockSparseAttention.bigbird_block_sparse_attention)
+ * on every query row whose own mask is 1; a masked position as a query still gets a row, by the rule below.
+ * q/k/v: column slices of the [B*S, 3H] projection (row stride ld >= 3 NH 64), head h at columns h*64..; attention_mask
+ * int64 [B,S] (0 = masked key) or NULL; out bf16 [B*S, ldo]; lse fp32 [B,NH,S]. nb = S / 64 blocks per sequence.
+ * LISTS (device int32): key_blocks / key_mult [NH, nb, nb], key_count [NH, nb] - the first key_count[h][i] entries (j, m)
+ * of row (h, i) are the key blocks the queries of block i of head h attend to and their multiplicities. The 64 queries of
+ * a block take ONE softmax over the keys of the listed blocks, a key of an entry (j, m) counting m times (HuggingFace
+ * concatenates the gathered blocks and does not remove duplicates): l += m sum exp, O += m P V, lse includes the m.
+ * stonkgs_amd/bigbird_attention.py builds BigBird's lists (global, window and random blocks) and their inverses.
+ * A masked key has probability exactly 0 and gets exactly zero dk / dv - unless ALL listed keys of a query block are
+ * masked: its rows then attend uniformly over the listed keys, weighted by multiplicity (the dense kernels' rule, per
+ * block; forward and backward agree, the block's lse entries are finite, about -2^100 * scale, and meaningless).
+ * The launcher cannot read the lists: a count outside [0, nb] (the list counts as empty), an entry outside [0, nb) or a
+ * multiplicity <= 0 (the entry is skipped) touches no memory through the bad value and sets bit 0 of *err_flag; a block
+ * without a valid entry writes zeros. Each list array must hold the full [NH, nb, nb] / [NH, nb] extent.
+ * Refused before any launch: q / k / v / a list / out / lse / err_flag null, scale <= 0 (STONK_EINVAL); D != 64, S % 64,
+ * S < 320, S > 4096, NH <= 0, B < 0, ld < 3 NH 64, ldo < NH 64 (STONK_ESHAPE); ld % 8, ldo % 4, q / k / v not 16-byte
+ * aligned, out not 8-byte aligned (STONK_EALIGN). B == 0 returns STONK_OK. */
+int stonk_block_sparse_attention_fwd(const void* q, const void* k, const void* v, int64_t ld, const int64_t* attention_mask,
+                                     const int* key_blocks, const int* key_mult, const int* key_count, void* out, int64_t ldo,
+                                     float* lse, int B, int NH, int S, int D, float scale, int* err_flag, void* stream);
+/* Backward of the above: recomputes P from lse, three launches (row statistics, dq, dk / dv), no atomics, bitwise
+ * repeatable. query_blocks / query_mult [NH, nb, nb], query_count [NH, nb]: the INVERSE lists - for key block j of head h
+ * the query blocks that list it, with the multiplicity they list it with (the same multiset of pairs as the forward
+ * lists; they fall under the same checks and the same err_flag bit). delta_ws: fp32 [2, B, NH, S] scratch (rowsum(dO * O),
+ * then -lse in log2 units). dq / dk / dv: bf16, row stride ldd >= NH 64, every row of every sequence is written.
+ * Refused as the forward, plus: a null inverse list / out / dout / lse / delta_ws / dq / dk / dv (STONK_EINVAL); lddo or
+ * ldd < NH 64 (STONK_ESHAPE); ldo % 8, lddo % 8, ldd % 4, out / dout not 16-byte or dq / dk / dv not 8-byte aligned
+ * (STONK_EALIGN). */
+int stonk_block_sparse_attention_bwd(const void* q, const void* k, const void* v, int64_t ld, const int64_t* attention_mask,
+                                     const int* key_blocks, const int* key_mult, const int* key_count, const int* query_blocks,
+                                     const int* query_mult, const int* query_count, const void* out, int64_t ldo,
+                                     const void* dout, int64_t lddo, const float* lse, float* delta_ws, void* dq, void* dk,
+                                     int64_t ldd, void* dv, int B, int NH, int S, int D, float scale, int* err_flag,
+                                     void* stream);
+
 /* P = softmax(q k^T * scale + key mask), written out. Forward-only, no dropout, PADDED layout only (csrc/attention_probs.hip).
  * q/k: column slices of the [B*S, 3H] projection (row stride ld), head h at columns h*64.. ; attention_mask int64 [B,S]
  * (0 = masked key) or NULL. probs (nullable): fp32 [B, NH, S, S], contiguous (HF `attentions` layout), 16-byte aligned.

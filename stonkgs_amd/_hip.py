@@ -61,6 +61,11 @@ _SIGNATURES = {
                             _i32, _i32, _i32, _f32, _f32, _u32, _vp],
     "stonk_attention_bwd_phases": [_i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp,
                                    _i32, _i32, _i32, _i32, _f32, _f32, _u32, _vp],
+    # block-sparse (BigBird) attention driven by per-block lists (csrc/bigbird_attention.hip)
+    "stonk_block_sparse_attention_fwd": [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _f32,
+                                         _vp, _vp],
+    "stonk_block_sparse_attention_bwd": [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp,
+                                         _vp, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp],
     "stonk_attention_probs": [_vp, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp],
     "stonk_transpose_bf16": [_vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp],
     "stonk_transpose_f32_to_bf16": [_vp, _vp, _i64, _i32, _i64, _vp],
