@@ -12,11 +12,12 @@ from __future__ import annotations
 
 import collections
 import contextlib
-
+import dataclasses
 import math
 import os
+import struct
 import time
-from typing import Callable, Dict, List, Optional
+from typing import Callable, Dict, Optional
 
 import torch
 
@@ -29,6 +30,68 @@ BF16, F32, I32 = torch.bfloat16, torch.float32, torch.int32
 ERR_BITS = {1: "entity id outside the KG table (the reference raises KeyError, stonkgs_model.py:185)",
             2: "token_type_id outside [0, type_vocab_size)", 4: "text token id outside the LM vocabulary",
             8: "MLM/ELM label outside the decoder's class range", 16: "NSP label outside [0, 2)"}
+
+Decoder = collections.namedtuple("Decoder", "name label_key weight classes offset")
+
+
+def decoders(cfg: STonKGsConfig):
+    """The two label-sparse decoders of the pre-training head, in the order of the loss terms (backward runs them in
+    reverse: the flat gradient buffer's order). `offset`: the first sequence position a decoder predicts."""
+    return (Decoder("text", "masked_lm_labels", "cls.predictions.text_decoder.weight", cfg.vocab_size, 0),
+            Decoder("ent", "ent_masked_lm_labels", "cls.predictions.entity_decoder.weight", cfg.kg_vocab_size,
+                    cfg.half_length))
+
+
+@dataclasses.dataclass(frozen=True)
+class ReadRows:
+    """The READ rows of the packed layout (labelled positions + position 0), on which the last encoder layer's
+    feed-forward block, the pooler and the head transform run (`Engine.prune_last_ffn`)."""
+    rows: torch.Tensor      # int32: packed row of every read row
+    cnt: torch.Tensor       # int32 [1]: their number, on the device ...
+    n: int                  # ... and on the host
+    offsets: torch.Tensor   # int32 [B + 1]: a sequence's read rows (its FIRST packed rows) among all read rows
+    T: int                  # n rounded up to 64
+    attn: bool              # the last layer's attention computes them alone as queries (`Engine.prune_last_attn`)
+
+
+@dataclasses.dataclass(frozen=True)
+class Rows:
+    """What one step knows about its rows. Padded layout: every position is a row, T = rows = B * S, `mask` = the
+    attention mask [B, S] (or None). Packed layout (csrc/unpad.hip, `Engine.unpad`): `cu` = sequence offsets, `mask` = one
+    word per row, the three maps of the row plan, and `rd` where the last layer runs on the read rows only."""
+    B: int
+    S: int
+    T: int                  # rows the layers run on (packed: the packed row count rounded up to 64)
+    rows: int               # rows that belong to a sequence
+    mask: Optional[torch.Tensor]
+    cu: Optional[torch.Tensor] = None
+    row_of_pos: Optional[torch.Tensor] = None
+    pos_of_row: Optional[torch.Tensor] = None
+    read_of_pos: Optional[torch.Tensor] = None
+    rd: Optional[ReadRows] = None
+
+    @property
+    def packed(self) -> bool:
+        return self.cu is not None
+
+    @property
+    def Th(self) -> int:
+        """Rows of the sequence output (and of everything the heads run on)."""
+        return self.T if self.rd is None else self.rd.T
+
+    @property
+    def first_rows(self) -> Optional[torch.Tensor]:
+        """Packed: row of position 0 of every sequence in the sequence output."""
+        return self.cu if self.rd is None else self.rd.offsets
+
+    @property
+    def head_map(self) -> Optional[torch.Tensor]:
+        """Packed: position -> row of the sequence output."""
+        return self.row_of_pos if self.rd is None else self.read_of_pos
+
+
+def padded_rows(B: int, S: int, mask) -> Rows:
+    return Rows(B, S, B * S, B * S, mask)
 
 
 class GemmTimer:
@@ -158,7 +221,7 @@ class Engine:
         self.sumsq_valid: set = set()
         self._sumsq_tiles: Dict[str, int] = {}
         self._sumsq_buf: Optional[torch.Tensor] = None
-        # Inputs-only backward (`input_gradients`, which alone sets it): the chain of dgrad GEMMs, LayerNorm and attention
+        # Inputs-only backward (`input_gradients` alone sets it, through `_detached`): the chain of dgrad GEMMs, LayerNorm and attention
         # backward runs down to d(embedding sum) and nothing is written to the gradient buffer - `wgrad` returns at once,
         # `ln_bwd` passes null dgamma / dbeta, the small linear layers' weight gradients go to scratch, stonk_embed_grad
         # and the `notify` hooks are skipped. False: every path issues exactly the launches it issued before the flag.
@@ -389,13 +452,6 @@ class Engine:
         hip.call("stonk_scatter_rows_bf16", src.data_ptr(), H, rd_rows.data_ptr(), cnt.data_ptr(), dst.data_ptr(), H, H,
                  hip.stream_ptr())
 
-    def transpose(self, x, rows, cols, name, colsum=None, rows_dev=None):
-        rpad = (rows + 63) // 64 * 64
-        out = self.buf(name, (cols, rpad))
-        hip.call("stonk_transpose_bf16", x.data_ptr(), x.stride(0), out.data_ptr(), rpad, rows, cols, hip.ptr(colsum),
-                 hip.ptr(rows_dev), hip.stream_ptr())
-        return out
-
     def _kernel(self, site: str, persistent_in_backward: bool = False) -> int:
         """NT kernel of a launch site: a tool's pin, else the dispatcher-scheduled form for a backward launch that
         would otherwise be persistent while a collective holds CUs, else the library's own choice."""
@@ -450,10 +506,8 @@ class Engine:
         """Descriptor table of the batched W^T refresh (stonk_transpose_bf16_batched): one entry per dgrad weight - source =
         its slice of the bf16 mirror (bit-identical to casting the fp32 master), destination = the [in, out_padded] copy.
         Addresses are stable for the life of the store, so the table is built once."""
-        import struct
-
         entries, first = [], 0
-        for name, off, rows, prows, cols, rpad, src, wt in self._wt_weights():
+        for _, _, rows, _, cols, rpad, src, wt in self._wt_weights():
             col_tiles = (cols + 63) // 64
             entries.append(struct.pack("<QQqqqiiii", src.data_ptr(), wt.data_ptr(), cols, rpad, rows, cols, first, col_tiles, 0))
             first += ((rows + 63) // 64) * col_tiles
@@ -467,10 +521,8 @@ class Engine:
         key = (self.P.data.data_ptr(), self.P.bf16.data_ptr())
         if self._adamw_tables is not None and self._adamw_tables[-1] == key:
             return self._adamw_tables[:-1]
-        import struct
-
         entries, first, spans, chunks, pos = [], 0, [], 0, 0
-        for name, off, rows, prows, cols, rpad, src, wt in self._wt_weights():
+        for name, off, rows, prows, cols, rpad, _, wt in self._wt_weights():
             if off < pos or (prows * cols) % 4:
                 raise ValueError(f"{name}: the flat buffer's order or alignment does not fit the tiled optimizer step")
             if off > pos:
@@ -491,19 +543,20 @@ class Engine:
         return self._adamw_tables[:-1]
 
     # ------------------------------------------------------------------ one BERT layer
-    def layer_fwd(self, S: FlatStore, prefix: str, x, B, seq, mask, p_hid, p_att, lidx, save: Optional[dict],
-                  T: Optional[int] = None, cu=None, rd: Optional[dict] = None, attn_maps: Optional[tuple] = None):
-        """One BERT layer on T rows. Padded layout: T = B * seq, `mask` = attention_mask [B, seq]. Packed layout (`cu` =
-        sequence offsets of stonk_unpad_plan): T = the packed row count rounded up to 64, `mask` = one word per row.
-        `rd` (last layer of the packed layout): the feed-forward block runs on the READ rows only - gathered after the
-        attention block's LayerNorm - and the layer's output has rd["T"] rows.
+    def layer_fwd(self, S: FlatStore, prefix: str, x, L: Rows, p_hid, p_att, lidx, save: Optional[dict],
+                  last: bool = False, attn_maps: Optional[tuple] = None):
+        """One BERT layer on the L.T rows of the layout `L` (`Rows`).
+        `last` (the layer whose output only the pooler and the heads read) with read rows in the layout: the feed-forward
+        block runs on the READ rows only - gathered after the attention block's LayerNorm, or (`rd.attn`) behind the
+        attention core - and the layer's output has L.rd.T rows.
         `attn_maps` (padded layout only): (probs fp32 [B, NH, seq, seq] or None, modal_mass fp32 [B, NH, seq, 2] or None,
         half) - this layer's attention probabilities at p = 0 are written there (stonk_attention_probs), from the `qkv`
         buffer right behind the projection: a forward-only pass reuses that buffer from layer to layer."""
         cfg = self.cfg
         H, I, NH = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads
+        B, seq, T, mask, cu = L.B, L.S, L.T, L.mask, L.cu
+        rd = L.rd if last else None
         cap = B * seq
-        T = cap if T is None else T
         st = hip.stream_ptr()
         tag = prefix if save is not None else "tmp"
         w = S.bf16_view
@@ -521,17 +574,17 @@ class Engine:
         # attention kernel and must stay finite for the projections that run over them)
         ctx = self.buf(f"{tag}.ctx", (cap, H), zero=True)
         lse = self.buf(f"{tag}.lse", (B, NH, seq), F32)
-        qattn = rd is not None and rd.get("attn", False)   # queries = the read rows only (a sequence's first rows)
-        qoff = rd["offsets"] if qattn else None
+        qattn = rd is not None and rd.attn   # queries = the read rows only (a sequence's first rows)
+        qoff = rd.offsets if qattn else None
         hip.call("stonk_attention_fwd", qkv.data_ptr(), qkv.data_ptr() + 2 * H, qkv.data_ptr() + 4 * H, 3 * H,
                  hip.ptr(mask), hip.ptr(cu), hip.ptr(qoff), ctx.data_ptr(), H, lse.data_ptr(), B, NH, seq, 64,
                  1.0 / math.sqrt(64.0), p_att, self.seed(lidx, 1), st)
         Ta, a_in, res = T, ctx, x                  # rows / input / residual of the output projection
         if qattn:
-            Ta = rd["T"]
+            Ta = rd.T
             a_in, res = self.buf(f"{tag}.ctxrd", (cap, H)), self.buf(f"{tag}.xrd", (cap, H))
-            self._gather_rows(ctx, rd["rows"], rd["cnt"], a_in, cap)
-            self._gather_rows(x, rd["rows"], rd["cnt"], res, cap)
+            self._gather_rows(ctx, rd.rows, rd.cnt, a_in, cap)
+            self._gather_rows(x, rd.rows, rd.cnt, res, cap)
         s1 = self.buf(f"{tag}.s1", (cap, H))
         fl = hip.EPI_BIAS | hip.EPI_RESID | (hip.EPI_DROPOUT if p_hid > 0 else 0)
         self.gemm(a_in, w(prefix + ".attention.output.dense.weight"), s1, Ta, H, H, flags=fl,
@@ -544,8 +597,8 @@ class Engine:
                  st1[1].data_ptr(), Ta, H, cfg.layer_norm_eps, 0, 0.0, 0, st)
         hf, Tf = h1, Ta                            # input rows of the feed-forward block
         if rd is not None and not qattn:
-            hf, Tf = self.buf(f"{tag}.h1rd", (cap, H)), rd["T"]
-            self._gather_rows(h1, rd["rows"], rd["cnt"], hf, cap)
+            hf, Tf = self.buf(f"{tag}.h1rd", (cap, H)), rd.T
+            self._gather_rows(h1, rd.rows, rd.cnt, hf, cap)
         g = self.buf(f"{tag}.g", (cap, I))
         u = self.buf(f"{tag}.u", (cap, I)) if save is not None else None
         fl = hip.EPI_BIAS | hip.EPI_GELU | ((hip.EPI_SAVE_PREACT | hip.EPI_AUX_GRAD) if save is not None else 0)
@@ -564,15 +617,15 @@ class Engine:
             save[prefix] = dict(x=x, qkv=qkv, ctx=ctx, ctx_in=a_in, lse=lse, s1=s1, h1=hf, st1=st1, g=g, u=u, s2=s2, st2=st2)
         return y
 
-    def layer_bwd(self, prefix: str, dy, B, seq, mask, p_hid, p_att, lidx, sv, T: Optional[int] = None, cu=None,
-                  rows: Optional[int] = None, rd: Optional[dict] = None):
-        """dy: bf16 [T,H] gradient of the layer output. Returns the gradient of the layer input. Packed layout: `cu`,
-        per-row `mask`, T = packed rows rounded up to 64, `rows` = the packed rows that belong to a sequence. `rd`: the
-        feed-forward block ran on the read rows (dy has rd["T"] rows); its input gradient is scattered back to all rows."""
+    def layer_bwd(self, prefix: str, dy, L: Rows, p_hid, p_att, lidx, sv, last: bool = False):
+        """dy: bf16 [T,H] gradient of the layer output. Returns the gradient of the layer input. `L`, `last`: the
+        forward's (`layer_fwd`). Where the feed-forward block ran on the read rows, dy has L.rd.T rows and its input
+        gradient is scattered back to all rows."""
         cfg = self.cfg
         H, I, NH = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads
+        B, seq, T, mask, cu = L.B, L.S, L.T, L.mask, L.cu
+        rd = L.rd if last else None
         cap = B * seq
-        T = cap if T is None else T
         st = hip.stream_ptr()
         P = self.P
         g_ = P.grad_view
@@ -587,7 +640,7 @@ class Engine:
         # ---- LN2 backward: ds2 (residual branch) and df (through the FFN-output dropout)
         ds2 = self.buf(f"b.ds2.{par}", (cap, H))
         df = self.buf(f"b.df.{par}", (cap, H)) if p_hid > 0 else None
-        Tf = T if rd is None else rd["T"]          # rows the feed-forward block ran on
+        Tf = T if rd is None else rd.T             # rows the feed-forward block ran on
         self.ln_bwd(dy, sv["s2"], sv["st2"][0], sv["st2"][1], f(prefix + ".output.LayerNorm.weight"), ds2, df,
                     g_(prefix + ".output.LayerNorm.weight"), g_(prefix + ".output.LayerNorm.bias"), Tf, H, 0, 0.0, 0, p_hid,
                     self.seed(lidx, 3))
@@ -601,17 +654,15 @@ class Engine:
         # ---- FFN up
         self.wgrad(du, sv["h1"], g_(prefix + ".intermediate.dense.weight"), g_(prefix + ".intermediate.dense.bias"), I, H,
                    Tf)
-        qattn = rd is not None and rd.get("attn", False)
+        qattn = rd is not None and rd.attn
         Ta = Tf if qattn else T                    # rows the attention block's projection / LayerNorm ran on
         dh1 = self.buf("b.dh1", (cap, H))
-        if rd is None or qattn:
-            self.gemm(du, wt[prefix + ".intermediate.dense.weight"], dh1, Tf, H, I, flags=hip.EPI_RESID, resid=ds2,
-                      kernel=self._kernel("dgrad_resid", True))
-        else:   # gradient of the gathered rows, scattered into an otherwise zero gradient of the attention block's output
-            dh1rd = self.buf("b.dh1rd", (cap, H))
-            self.gemm(du, wt[prefix + ".intermediate.dense.weight"], dh1rd, Tf, H, I, flags=hip.EPI_RESID, resid=ds2,
-                      kernel=self._kernel("dgrad_resid", True))
-            self._scatter_rows_into_zeros(dh1rd, rd["rows"], rd["cnt"], dh1, T)
+        gathered = rd is not None and not qattn    # the feed-forward block alone ran on gathered rows
+        dh1f = self.buf("b.dh1rd", (cap, H)) if gathered else dh1
+        self.gemm(du, wt[prefix + ".intermediate.dense.weight"], dh1f, Tf, H, I, flags=hip.EPI_RESID, resid=ds2,
+                  kernel=self._kernel("dgrad_resid", True))
+        if gathered:   # their gradient, scattered into an otherwise zero gradient of the attention block's output
+            self._scatter_rows_into_zeros(dh1f, rd.rows, rd.cnt, dh1, T)
         # ---- LN1 backward
         ds1 = self.buf(f"b.ds1.{par}", (cap, H))
         da = self.buf(f"b.da.{par}", (cap, H)) if p_hid > 0 else None
@@ -624,21 +675,18 @@ class Engine:
         self.wgrad(da, sv["ctx_in"], g_(prefix + ".attention.output.dense.weight"),
                    g_(prefix + ".attention.output.dense.bias"), H, H, Ta)
         dctx = self.buf("b.dctx", (cap, H))
-        if not qattn:
-            self.gemm(da, wt[prefix + ".attention.output.dense.weight"], dctx, T, H, H,
-                      kernel=self._kernel("dgrad_attn_out", True))
-        else:   # the read rows' gradients go back to their packed rows: into zeros (the kernels read whole query tiles)
-            dctxrd, ds1rd = self.buf("b.dctxrd", (cap, H)), ds1
-            self.gemm(da, wt[prefix + ".attention.output.dense.weight"], dctxrd, Ta, H, H,
-                      kernel=self._kernel("dgrad_attn_out", True))
-            ds1 = self.buf("b.ds1full", (cap, H))
-            self._scatter_rows_into_zeros(dctxrd, rd["rows"], rd["cnt"], dctx, T)
-            self._scatter_rows_into_zeros(ds1rd, rd["rows"], rd["cnt"], ds1, T)
+        dctxa = self.buf("b.dctxrd", (cap, H)) if qattn else dctx
+        self.gemm(da, wt[prefix + ".attention.output.dense.weight"], dctxa, Ta, H, H,
+                  kernel=self._kernel("dgrad_attn_out", True))
+        if qattn:   # the read rows' gradients go back to their packed rows: into zeros (the kernels read whole query tiles)
+            ds1rd, ds1 = ds1, self.buf("b.ds1full", (cap, H))
+            self._scatter_rows_into_zeros(dctxa, rd.rows, rd.cnt, dctx, T)
+            self._scatter_rows_into_zeros(ds1rd, rd.rows, rd.cnt, ds1, T)
         # ---- attention core
         qkv = sv["qkv"]
         dqkv = self.buf(f"b.dqkv.{par}", (cap, 3 * H))
         delta = self.buf("b.delta", (B, NH, seq), F32)
-        qoff = rd["offsets"] if qattn else None
+        qoff = rd.offsets if qattn else None
         if qattn:
             # dQ of the rows that were not queries (the kernel does not write them) feeds the projection's gradients; their dK and
             # dV are the dK/dV kernel's to write (every key row of a sequence), so only the dQ third is cleared: 40 of 122 MB
@@ -678,8 +726,9 @@ class Engine:
                  f("lm_backbone.embeddings.LayerNorm.bias").data_ptr(), x.data_ptr(), B, seq, H, cfg.vocab_size,
                  cfg.layer_norm_eps, hip.LN_DROPOUT if p_hid > 0 else 0, p_hid, self.seed(100, 0), self.err.data_ptr(),
                  hip.stream_ptr())
+        L = padded_rows(B, seq, mask)
         for i in range(self.n_bb):
-            x = self.layer_fwd(self.BB, f"lm_backbone.encoder.layer.{i}", x, B, seq, mask, p_hid, p_att, 101 + i, None)
+            x = self.layer_fwd(self.BB, f"lm_backbone.encoder.layer.{i}", x, L, p_hid, p_att, 101 + i, None)
         return x
 
     def prefetch_backbone(self, input_ids, training: bool) -> None:
@@ -779,15 +828,14 @@ class Engine:
         return text_hidden, hint
 
     def encode(self, input_ids, attention_mask, token_type_ids, training: bool, save: dict, unpad_labels=None,
-               layout: Optional[dict] = None, attn_maps: Optional[dict] = None):
+               attn_maps: Optional[dict] = None):
         """F1-F4: frozen backbone, KG gather + embeddings LayerNorm, encoder layers, pooler. Shared by the pre-training
         and the sequence-classification models (ref:stonkgs_model.py:178-212, ref:stonkgs_finetuning.py:277-310).
         `unpad_labels`: None = padded layout (every position a row: callers that hand out hidden states or dense
         logits); a (text_labels, entity_labels) pair (either may be None) = packed layout, see `Engine.unpad`.
-        `layout` (a dict, forward-only callers that run heads of their own: `evaluate`): receives the rows of the
-        sequence output (`Th`) and the position -> row map of those rows (`head_map`, None in the padded layout).
         `attn_maps` (forward-only, padded layout, dropout off): {layer index: (probs or None, modal_mass or None)} - the
-        selected layers write their attention probabilities into these tensors (`layer_fwd`)."""
+        selected layers write their attention probabilities into these tensors (`layer_fwd`).
+        Returns (sequence output, pooled, the row layout `Rows`); `save` keeps the layout too (`save["layout"]`)."""
         cfg = self.cfg
         H, S, half = cfg.hidden_size, cfg.max_position_embeddings, self.half_length
         B = input_ids.shape[0]
@@ -805,27 +853,26 @@ class Engine:
             plan, ev = self._plan_rows(attention_mask, unpad_labels[0], unpad_labels[1], B, S, half, keep=save is not None)
         text_hidden, hint = self._text_half(input_ids, B, training)
         self.wait_params()   # everything above read frozen weights only; from here on the trainable ones
-        T, rows, cu, mask, rd = cap, cap, None, attention_mask, None
-        if plan is not None:
+        if plan is None:
+            L = padded_rows(B, S, attention_mask)
+            sq = sq_last = B * S * S
+        else:
             self.mark("plan_wait")
             ev.synchronize()                       # (a backbone forward - this batch's or the next one's - is queued: the GPU has work)
             self.mark("plan_known")
             host = self._plan_host[:2 * (B + 1)].tolist()
             offs, n_read = host[:B + 1], host[2 * B + 1]
-            rows = offs[B]
-            T = min(cap, (rows + 63) // 64 * 64)   # whole 64-row K tiles for the weight gradients; the tail rows are zeros
-            cu, mask = plan["cu"], plan["row_mask"]
-            sq = sum((offs[i + 1] - offs[i]) ** 2 for i in range(B))
+            rd = None
             if self.prune_last_ffn:
-                rd = dict(rows=plan["read_rows"], cnt=plan["cu_rd"][B:B + 1], n=n_read, offsets=plan["cu_rd"],
-                          T=min(cap, (n_read + 63) // 64 * 64), attn=self.prune_last_attn)
-        else:
-            sq = B * S * S
-        Th = T if rd is None else rd["T"]          # rows of the sequence output (and of everything the heads run on)
-        sq_last = sq
-        if rd is not None and rd["attn"]:
-            sq_last = sum((host[B + 2 + i] - host[B + 1 + i]) * (offs[i + 1] - offs[i]) for i in range(B))
-        for i, v in enumerate((T, cap, 1, sq, B * S * S, Th, sq_last)):
+                rd = ReadRows(rows=plan["read_rows"], cnt=plan["cu_rd"][B:B + 1], n=n_read, offsets=plan["cu_rd"],
+                              T=min(cap, (n_read + 63) // 64 * 64), attn=self.prune_last_attn)
+            # T: whole 64-row K tiles for the weight gradients; the tail rows are zeros
+            L = Rows(B, S, T=min(cap, (offs[B] + 63) // 64 * 64), rows=offs[B], mask=plan["row_mask"], cu=plan["cu"],
+                     row_of_pos=plan["row_of_pos"], pos_of_row=plan["pos_of_row"], read_of_pos=plan["read_of_pos"], rd=rd)
+            sq = sq_last = sum((offs[i + 1] - offs[i]) ** 2 for i in range(B))
+            if rd is not None and rd.attn:
+                sq_last = sum((host[B + 2 + i] - host[B + 1 + i]) * (offs[i + 1] - offs[i]) for i in range(B))
+        for i, v in enumerate((L.T, cap, 1, sq, B * S * S, L.Th, sq_last)):
             self.rows_executed[i] += v
         # F2 gather + concat + embeddings LayerNorm
         # (a forward-only call - save is None - works in scratch buffers of its own throughout: it may run between a
@@ -840,8 +887,7 @@ class Engine:
                  f("bert.embeddings.LayerNorm.weight").data_ptr(), f("bert.embeddings.LayerNorm.bias").data_ptr(),
                  sum0.data_ptr(), x.data_ptr(), st0[0].data_ptr(), st0[1].data_ptr(), B, S, half, H,
                  self.kg_table.shape[0], cfg.type_vocab_size, cfg.layer_norm_eps, hip.LN_DROPOUT if p_hid > 0 else 0,
-                 p_hid, self.seed(200, 0), self.err.data_ptr(), 0 if plan is None else plan["pos_of_row"].data_ptr(),
-                 T if plan is not None else 0, st)
+                 p_hid, self.seed(200, 0), self.err.data_ptr(), hip.ptr(L.pos_of_row), L.T if L.packed else 0, st)
         if hint is not None:   # (after an inline backbone forward: behind the kernel above, the last reader of its scratch)
             self.prefetch_backbone(hint, training)
         # F3 encoder
@@ -851,44 +897,40 @@ class Engine:
         for i in range(cfg.num_hidden_layers):
             with self.block(f"K4-K8 encoder layer {i} fwd"):
                 am = attn_maps.get(i) if attn_maps else None
-                x = self.layer_fwd(P, f"bert.encoder.layer.{i}", x, B, S, mask, p_hid, p_att, i, save, T=T, cu=cu,
-                                   rd=rd if i == last else None, attn_maps=None if am is None else (am[0], am[1], half))
+                x = self.layer_fwd(P, f"bert.encoder.layer.{i}", x, L, p_hid, p_att, i, save, last=i == last,
+                                   attn_maps=None if am is None else (am[0], am[1], half))
         self._span_end("encoder_fwd", span)
-        seq_out = x                                # [Th rows]: every packed row, or the read rows only
+        seq_out = x                                # [L.Th rows]: every packed row, or the read rows only
         # F4 pooler (fp32 master weights) on position 0 of every sequence
         pooled = self.buf(f"{e}.pooled", (B, H), F32)
-        first_rows = None if plan is None else (cu if rd is None else plan["cu_rd"])
-        if plan is None:
+        if not L.packed:
             first, ld_first = seq_out, S * H
         else:   # packed: position 0 of sequence b is row cu[b] (among the read rows: read_offsets[b])
             nb = self.buf(f"{e}.nb", (1,), I32)
             nb.fill_(B)
             first, ld_first = self.buf(f"{e}.first", ((B + 127) // 128 * 128, H)), H
-            self._gather_rows(seq_out, first_rows, nb, first, first.shape[0])
+            self._gather_rows(seq_out, L.first_rows, nb, first, first.shape[0])
         hip.call("stonk_small_linear_fwd", first.data_ptr(), ld_first, f("bert.pooler.dense.weight").data_ptr(),
                  f("bert.pooler.dense.bias").data_ptr(), pooled.data_ptr(), B, H, H, hip.SMALL_TANH, st)
         if save is not None:   # (None: forward-only callers - embedding extraction, batched inference)
-            save.update(B=B, input_ids=input_ids, attention_mask=mask, token_type_ids=token_type_ids, sum0=sum0, st0=st0,
-                        seq_out=seq_out, pooled=pooled, p_hid=p_hid, p_att=p_att, T=T, rows=rows, plan=plan,
-                        first=first, ld_first=ld_first, rd=rd, Th=Th, first_rows=first_rows, text_hidden=text_hidden,
-                        head_map=None if plan is None else (plan["row_of_pos"] if rd is None else plan["read_of_pos"]))
-        if layout is not None:
-            layout.update(Th=Th, head_map=None if plan is None else (plan["row_of_pos"] if rd is None else plan["read_of_pos"]))
-        return seq_out, pooled
+            save.update(layout=L, input_ids=input_ids, token_type_ids=token_type_ids, sum0=sum0, st0=st0, seq_out=seq_out,
+                        pooled=pooled, p_hid=p_hid, p_att=p_att, first=first, ld_first=ld_first, text_hidden=text_hidden)
+        return seq_out, pooled, L
 
-    def _sparse_head(self, pre, nm, wname, N, off, labels, t, row_of_pos, cnt, loss_sum, B, need_backward,
+    def _sparse_head(self, pre, dec: Decoder, labels, t, row_of_pos, cnt, loss_sum, B, need_backward,
                      grad_scale: float = 1.0):
         """One label-sparse decoder + fused cross-entropy (F6), shared by the training forward (`pre` = "l") and `evaluate`
         ("ev": small buffers of its own, so that it may run between a forward and its backward): compaction of the labelled
         positions into rows of `t` (through `row_of_pos` in the packed layout), row gather, decoder GEMM over the
         device-side count, cross-entropy into `loss_sum` (+ dlogits when `need_backward`). The logits buffer is the same
         for both callers - nothing reads it after the call that filled it. `grad_scale`: dlogits = (softmax - onehot) *
-        grad_scale / count. Returns (rows, targets, cnt, hs, logits, dl)."""
+        grad_scale / count. Returns dict(rows, tg, cnt, hs, logits, dl)."""
         H, S, half = self.cfg.hidden_size, self.cfg.max_position_embeddings, self.cfg.half_length
+        nm, N = dec.name, dec.classes
         cap, npad, st = B * half, pad128(N), hip.stream_ptr()
         rows = self.buf(f"{pre}.{nm}.rows", (cap,), I32)
         tg = self.buf(f"{pre}.{nm}.tg", (cap,), I32)
-        hip.call("stonk_label_compact", labels.data_ptr(), cap, half, S, off, rows.data_ptr(), tg.data_ptr(),
+        hip.call("stonk_label_compact", labels.data_ptr(), cap, half, S, dec.offset, rows.data_ptr(), tg.data_ptr(),
                  cnt.data_ptr(), hip.ptr(row_of_pos), st)
         hs = self.buf(f"{pre}.{nm}.hs", (cap, H))
         self._gather_rows(t, rows, cnt, hs, cap)
@@ -896,24 +938,31 @@ class Engine:
         # decoder GEMM writes and the cross-entropy reads 2 bytes per logit instead of 4 - both are HBM-bound on them
         f16 = self.f16_logits
         logits = self.buf(f"l.{nm}.logits", (cap, npad), torch.float16 if f16 else F32)
-        self.gemm(hs, self.P.bf16_view(wname), logits, cap, npad, H, flags=hip.EPI_OUT_F16 if f16 else hip.EPI_OUT_F32,
+        self.gemm(hs, self.P.bf16_view(dec.weight), logits, cap, npad, H, flags=hip.EPI_OUT_F16 if f16 else hip.EPI_OUT_F32,
                   m_dev=cnt)
         dl = self.buf(f"{pre}.{nm}.dl", (cap, npad)) if need_backward else None
         hip.call("stonk_softmax_xent_f16_fwd_bwd" if f16 else "stonk_softmax_xent_fwd_bwd", logits.data_ptr(), npad,
                  N, npad, tg.data_ptr(), cnt.data_ptr(), loss_sum.data_ptr(), hip.ptr(dl), npad, grad_scale, cap,
                  self.err.data_ptr(), st)
-        return rows, tg, cnt, hs, logits, dl
+        return dict(rows=rows, tg=tg, cnt=cnt, hs=hs, logits=logits, dl=dl)
 
-    def _head_transform(self, pre, seq_out, pooled, T, B, save_preact: bool):
-        """F4b / F5 on T rows of the sequence output: NSP logits from the pooled vector, then dense + GELU + LayerNorm of
-        the prediction head, in buffers named by `pre` ("h": training forward, "ev": `evaluate`). Returns (nsp, gt, ut, t,
-        stt); `ut` (the saved pre-activation) only with `save_preact`."""
+    def _pooled_linear(self, name, out, x, B, C):
+        """The fp32 linear layer `name` (H -> C: the NSP head, the classifier) on the B pooled rows `x`, into the buffer
+        `out` (fp32 [B, C], returned)."""
+        H, f = self.cfg.hidden_size, self.P.view
+        y = self.buf(out, (B, C), F32)
+        hip.call("stonk_small_linear_fwd", x.data_ptr(), H, f(name + ".weight").data_ptr(), f(name + ".bias").data_ptr(),
+                 y.data_ptr(), B, C, H, hip.SMALL_X_F32, hip.stream_ptr())
+        return y
+
+    def _head_transform(self, pre, seq_out, pooled, L: Rows, save_preact: bool):
+        """F4b / F5 on the rows of the sequence output: NSP logits from the pooled vector, then dense + GELU + LayerNorm of
+        the prediction head, in buffers named by `pre` ("h": training forward, "ev": `evaluate`). Returns (nsp, what the
+        backward reads: dict(gt, ut, t, stt)); `ut` (the saved pre-activation) only with `save_preact`."""
         cfg = self.cfg
-        H, cap_rows, st = cfg.hidden_size, B * cfg.max_position_embeddings, hip.stream_ptr()
+        H, cap_rows, T, st = cfg.hidden_size, L.B * L.S, L.Th, hip.stream_ptr()
         f, w = self.P.view, self.P.bf16_view
-        nsp = self.buf(f"{pre}.nsp", (B, 2), F32)
-        hip.call("stonk_small_linear_fwd", pooled.data_ptr(), H, f("cls.seq_relationship.weight").data_ptr(),
-                 f("cls.seq_relationship.bias").data_ptr(), nsp.data_ptr(), B, 2, H, hip.SMALL_X_F32, st)
+        nsp = self._pooled_linear("cls.seq_relationship", f"{pre}.nsp", pooled, L.B, 2)
         gt = self.buf(f"{pre}.gt", (cap_rows, H))
         ut = self.buf(f"{pre}.ut", (cap_rows, H)) if save_preact else None
         self.gemm(seq_out, w("cls.predictions.transform.dense.weight"), gt, T, H, H,
@@ -924,7 +973,18 @@ class Engine:
         hip.call("stonk_layernorm_fwd", gt.data_ptr(), f("cls.predictions.transform.LayerNorm.weight").data_ptr(),
                  f("cls.predictions.transform.LayerNorm.bias").data_ptr(), t.data_ptr(), stt[0].data_ptr(),
                  stt[1].data_ptr(), T, H, cfg.layer_norm_eps, 0, 0.0, 0, st)
-        return nsp, gt, ut, t, stt
+        return nsp, dict(gt=gt, ut=ut, t=t, stt=stt)
+
+    def _loss_tail(self, nsp, nsp_labels, acc, cnts, dnsp, B) -> dict:
+        """NSP cross-entropy (+ dlogits into `dnsp` unless None), then the four loss terms from the sums and counts in
+        `acc` [text_sum, ent_sum, nsp_sum, nsp_cnt, loss x4] / `cnts`. Returns the loss entries of a forward's result."""
+        st = hip.stream_ptr()
+        hip.call("stonk_nsp_xent_fwd_bwd", nsp.data_ptr(), nsp_labels.data_ptr(), B, 2, acc[2:4].data_ptr(),
+                 hip.ptr(dnsp), 1.0, self.err.data_ptr(), st)
+        hip.call("stonk_loss_finalize", acc[0:1].data_ptr(), cnts[0:1].data_ptr(), acc[1:2].data_ptr(),
+                 cnts[1:2].data_ptr(), acc[2:4].data_ptr(), acc[4:8].data_ptr(), st)
+        return dict(loss=acc[4], masked_lm_loss=acc[5], ent_masked_lm_loss=acc[6], next_sentence_loss=acc[7],
+                    loss_terms=acc[4:8])
 
     def forward(self, input_ids, attention_mask, token_type_ids, mlm_labels, ent_labels, nsp_labels, training: bool,
                 dense_logits: bool, need_backward: bool, want_hidden: bool = True):
@@ -933,76 +993,77 @@ class Engine:
         cfg = self.cfg
         H, S, half = cfg.hidden_size, cfg.max_position_embeddings, cfg.half_length
         B = input_ids.shape[0]
-        cap_rows = B * S
-        st = hip.stream_ptr()
-        P = self.P
-        f, w = P.view, P.bf16_view
         save: dict = {}
+        labels = dict(masked_lm_labels=mlm_labels, ent_masked_lm_labels=ent_labels)
         have_labels = mlm_labels is not None and ent_labels is not None and nsp_labels is not None
         packed = have_labels and not dense_logits and not want_hidden
-        seq_out, pooled = self.encode(input_ids, attention_mask, token_type_ids, training, save,
-                                      (mlm_labels, ent_labels) if packed else None)
-        T, plan = save["Th"], save["plan"]          # rows of the sequence output: all packed rows, or the read rows
-        row_of_pos = save["head_map"]
+        seq_out, pooled, L = self.encode(input_ids, attention_mask, token_type_ids, training, save,
+                                         (mlm_labels, ent_labels) if packed else None)
         # F5 head transform: dense + GELU, LayerNorm
-        nsp, gt, ut, t, stt = self._head_transform("h", seq_out, pooled, T, B, True)
-        out = dict(hidden_states=seq_out.view(B, S, H) if plan is None else None, pooler_output=pooled, nsp_logits=nsp)
-        heads = (("text", "cls.predictions.text_decoder.weight", cfg.vocab_size, 0, mlm_labels),
-                 ("ent", "cls.predictions.entity_decoder.weight", cfg.kg_vocab_size, half, ent_labels))
+        nsp, ht = self._head_transform("h", seq_out, pooled, L, True)
+        t = ht["t"]
+        out = dict(hidden_states=None if L.packed else seq_out.view(B, S, H), pooler_output=pooled, nsp_logits=nsp)
         # F6 label-sparse decoders + fused softmax cross-entropy (value and logits-gradient in one sweep)
         if have_labels:
             acc = self.buf("l.acc", (8,), F32)  # [text_sum, ent_sum, nsp_sum, nsp_cnt, loss x4]
             acc.zero_()
             cnts = self.buf("l.cnt", (2,), I32)
-            cap = B * half
-            for hi, (nm, wname, N, off, labels) in enumerate(heads):
-                rows, tg, cnt, hs, _, dl = self._sparse_head("l", nm, wname, N, off, labels, t, row_of_pos, cnts[hi:hi + 1],
-                                                             acc[hi:hi + 1], B, need_backward)
-                save[nm] = dict(rows=rows, cnt=cnt, hs=hs, dl=dl)
+            for hi, dec in enumerate(decoders(cfg)):
+                save[dec.name] = self._sparse_head("l", dec, labels[dec.label_key], t, L.head_map, cnts[hi:hi + 1],
+                                                   acc[hi:hi + 1], B, need_backward)
             dnsp = self.buf("l.dnsp", (B, 2), F32) if need_backward else None
-            hip.call("stonk_nsp_xent_fwd_bwd", nsp.data_ptr(), nsp_labels.data_ptr(), B, 2, acc[2:4].data_ptr(),
-                     hip.ptr(dnsp), 1.0, self.err.data_ptr(), st)
-            hip.call("stonk_loss_finalize", acc[0:1].data_ptr(), cnts[0:1].data_ptr(), acc[1:2].data_ptr(),
-                     cnts[1:2].data_ptr(), acc[2:4].data_ptr(), acc[4:8].data_ptr(), st)
-            out.update(loss=acc[4], masked_lm_loss=acc[5], ent_masked_lm_loss=acc[6], next_sentence_loss=acc[7],
-                       loss_terms=acc[4:8])
+            out.update(self._loss_tail(nsp, nsp_labels, acc, cnts, dnsp, B))
             save["dnsp"] = dnsp
         # F7 dense logits (what the reference always materialises: stonkgs_model.py:70-71)
         if dense_logits:
             cap = B * half
             full = self.buf("d.cnt", (1,), I32)
             full.fill_(cap)
-            for nm, wname, N, off, _ in heads:
-                npad = pad128(N)
-                rows = self.buf(f"d.{nm}.rows", (cap,), I32)
-                rows.copy_((torch.arange(cap, device=self.device, dtype=I32) // half) * S + off +
+            for dec in decoders(cfg):
+                N, npad = dec.classes, pad128(dec.classes)
+                rows = self.buf(f"d.{dec.name}.rows", (cap,), I32)
+                rows.copy_((torch.arange(cap, device=self.device, dtype=I32) // half) * S + dec.offset +
                            torch.arange(cap, device=self.device, dtype=I32) % half)
                 hs = self.buf("d.hs", (cap, H))
                 self._gather_rows(t, rows, full, hs, cap)
                 # fresh tensor: handed to the caller, must not alias the workspace
                 logits = torch.empty(cap, npad, dtype=F32, device=self.device)
-                self.gemm(hs, w(wname), logits, cap, npad, H, flags=hip.EPI_OUT_F32)
-                out[f"{nm}_logits"] = logits[:, :N].view(B, half, N)
+                self.gemm(hs, self.P.bf16_view(dec.weight), logits, cap, npad, H, flags=hip.EPI_OUT_F32)
+                out[f"{dec.name}_logits"] = logits[:, :N].view(B, half, N)
         if need_backward:
-            save.update(gt=gt, ut=ut, t=t, stt=stt)
+            save.update(ht)
             self.saved = save
         return out
+
+    # ------------------------------------------------------------------ calls that training must not notice
+    @contextlib.contextmanager
+    def _detached(self, restore_rows: bool, inputs_only: bool = False):
+        """Run the body detached from training: an `encode` in it neither consumes nor queues a frozen-backbone prefetch
+        nor advances the dropout counter for good - the prefetched forward, the hint for the next one, `seed_base` and
+        (`restore_rows`) `rows_executed` are put back on exit, whether the body returns or raises. The body's inline
+        backbone forward shares the prefetch's scratch buffers, so the stream is ordered behind a prefetch in flight.
+        `inputs_only`: `_inputs_only` is set for the body."""
+        seed_base, prefetch, hint, rows = self.seed_base, self._prefetch, self.next_input_ids, list(self.rows_executed)
+        self._prefetch = self.next_input_ids = None
+        if prefetch is not None:
+            torch.cuda.current_stream().wait_event(prefetch["done"])
+        self._inputs_only = inputs_only
+        try:
+            yield
+        finally:
+            self._inputs_only = False
+            self.seed_base, self._prefetch, self.next_input_ids = seed_base, prefetch, hint
+            if restore_rows:
+                self.rows_executed[:] = rows
 
     # ------------------------------------------------------------------ attention maps (forward-only, on request)
     def attention_maps(self, input_ids, attention_mask, token_type_ids, attn_maps: dict):
         """`encode` in the padded layout, eval mode, with the layers named in `attn_maps` writing their attention
         probabilities (see `encode`). Returns the pooled output (a workspace view). Invisible to training as `evaluate`
         is: scratch buffers of its own (save = None), the prefetched frozen-backbone forward, the hint for the next one
-        and the dropout counter are as they were."""
-        held = (self.seed_base, self._prefetch, self.next_input_ids)
-        self._prefetch = self.next_input_ids = None
-        if held[1] is not None:   # (the inline backbone forward shares the prefetch's scratch buffers)
-            torch.cuda.current_stream().wait_event(held[1]["done"])
-        try:
-            _, pooled = self.encode(input_ids, attention_mask, token_type_ids, False, None, None, attn_maps=attn_maps)
-        finally:
-            self.seed_base, self._prefetch, self.next_input_ids = held
-        return pooled
+        and the dropout counter are as they were; `rows_executed` counts the call."""
+        with self._detached(restore_rows=False):
+            return self.encode(input_ids, attention_mask, token_type_ids, False, None, None, attn_maps=attn_maps)[1]
 
     # ------------------------------------------------------------------ evaluation (forward-only, label-sparse)
     def evaluate(self, input_ids, attention_mask, token_type_ids, mlm_labels, ent_labels, nsp_labels, k: int = 10):
@@ -1018,105 +1079,46 @@ class Engine:
         store-mode gradient state, the gradient buffer and the dropout counter are as they were; every buffer a pending
         backward reads is left alone (own head buffers; the logits buffers are not saved for backward)."""
         cfg = self.cfg
-        H, S, half = cfg.hidden_size, cfg.max_position_embeddings, cfg.half_length
+        S, half = cfg.max_position_embeddings, cfg.half_length
         B = input_ids.shape[0]
-        cap_rows, cap = B * S, B * half
+        cap = B * half
         st = hip.stream_ptr()
-        f, w = self.P.view, self.P.bf16_view
-        # the encoder below must neither consume nor queue a frozen-backbone prefetch, nor advance the dropout counter; it
-        # shares the prefetch's scratch buffers, so it is ordered behind a prefetch in flight
-        held = (self.seed_base, self._prefetch, self.next_input_ids, list(self.rows_executed))
-        self._prefetch = self.next_input_ids = None
-        if held[1] is not None:
-            torch.cuda.current_stream().wait_event(held[1]["done"])
-        layout: dict = {}
-        try:
-            seq_out, pooled = self.encode(input_ids, attention_mask, token_type_ids, False, None, (mlm_labels, ent_labels),
-                                          layout=layout)
-        finally:
-            self.seed_base, self._prefetch, self.next_input_ids = held[:3]
-            self.rows_executed[:] = held[3]
-        T, head_map = layout["Th"], layout["head_map"]
-        nsp, _, _, t, _ = self._head_transform("ev", seq_out, pooled, T, B, False)
+        labels = dict(masked_lm_labels=mlm_labels, ent_masked_lm_labels=ent_labels)
+        with self._detached(restore_rows=True):
+            seq_out, pooled, L = self.encode(input_ids, attention_mask, token_type_ids, False, None,
+                                             (mlm_labels, ent_labels))
+        nsp, ht = self._head_transform("ev", seq_out, pooled, L, False)
         acc = self.buf("ev.acc", (8,), F32)   # [text_sum, ent_sum, nsp_sum, nsp_cnt, loss x4]
         acc.zero_()
         cnts = self.buf("ev.cnt", (2,), I32)
         out = dict(nsp_logits=nsp)
         f16 = self.f16_logits
-        for hi, (nm, wname, N, off, labels) in enumerate((
-                ("text", "cls.predictions.text_decoder.weight", cfg.vocab_size, 0, mlm_labels),
-                ("ent", "cls.predictions.entity_decoder.weight", cfg.kg_vocab_size, half, ent_labels))):
-            npad = pad128(N)
-            rows, tg, cnt, _, logits, _ = self._sparse_head("ev", nm, wname, N, off, labels, t, head_map, cnts[hi:hi + 1],
-                                                            acc[hi:hi + 1], B, False)
+        for hi, dec in enumerate(decoders(cfg)):
+            nm, N, npad = dec.name, dec.classes, pad128(dec.classes)
+            h = self._sparse_head("ev", dec, labels[dec.label_key], ht["t"], L.head_map, cnts[hi:hi + 1], acc[hi:hi + 1], B,
+                                  False)
+            tg, cnt = h["tg"], h["cnt"]
             # the caller wants flat positions b*S + off + p; in the packed layout the compaction above produced rows of the
             # sequence output instead (what the gather reads), so it runs once more without the map: one workgroup, ~20 us
-            pos = rows
-            if head_map is not None:
+            pos = h["rows"]
+            if L.packed:
                 pos = self.buf(f"ev.{nm}.pos", (cap,), I32)
-                hip.call("stonk_label_compact", labels.data_ptr(), cap, half, S, off, pos.data_ptr(), tg.data_ptr(),
-                         cnt.data_ptr(), 0, st)
+                hip.call("stonk_label_compact", labels[dec.label_key].data_ptr(), cap, half, S, dec.offset, pos.data_ptr(),
+                         tg.data_ptr(), cnt.data_ptr(), 0, st)
             top_val = self.buf(f"ev.{nm}.top_val", (cap, k), F32)
             top_idx = self.buf(f"ev.{nm}.top_idx", (cap, k), I32)
             lse = self.buf(f"ev.{nm}.lse", (cap,), F32)
             rank = self.buf(f"ev.{nm}.rank", (cap,), I32)
             tl = self.buf(f"ev.{nm}.tgt_logit", (cap,), F32)
-            hip.call("stonk_row_topk_f16" if f16 else "stonk_row_topk_f32", logits.data_ptr(), npad, N, tg.data_ptr(),
+            hip.call("stonk_row_topk_f16" if f16 else "stonk_row_topk_f32", h["logits"].data_ptr(), npad, N, tg.data_ptr(),
                      cnt.data_ptr(), cap, k, top_val.data_ptr(), top_idx.data_ptr(), lse.data_ptr(), rank.data_ptr(),
                      tl.data_ptr(), st)
             out[nm] = dict(rows=pos, targets=tg, count=cnt, top_idx=top_idx, top_val=top_val, lse=lse, rank=rank,
                            tgt_logit=tl)
-        hip.call("stonk_nsp_xent_fwd_bwd", nsp.data_ptr(), nsp_labels.data_ptr(), B, 2, acc[2:4].data_ptr(), 0, 1.0,
-                 self.err.data_ptr(), st)
-        hip.call("stonk_loss_finalize", acc[0:1].data_ptr(), cnts[0:1].data_ptr(), acc[1:2].data_ptr(),
-                 cnts[1:2].data_ptr(), acc[2:4].data_ptr(), acc[4:8].data_ptr(), st)
-        out.update(loss=acc[4], masked_lm_loss=acc[5], ent_masked_lm_loss=acc[6], next_sentence_loss=acc[7],
-                   loss_terms=acc[4:8], nsp_sum_cnt=acc[2:4])
+        out.update(self._loss_tail(nsp, nsp_labels, acc, cnts, None, B), nsp_sum_cnt=acc[2:4])
         return out
 
     # ------------------------------------------------------------------ input gradients (inputs-only backward)
-    def _attribution_heads(self, sv, heads, dnsp):
-        """Head part of the inputs-only backward of the pre-training model: for every decoder in `heads` (the `save`
-        entries of `_sparse_head`, dlogits = onehot - softmax) dgrad and scatter into d(head transform output), then the
-        head transform's LayerNorm and GELU backward and the dgrad into d(sequence_output); without a decoder that
-        gradient is zero. `dnsp` (fp32 [B, 2] or None): through the NSP classifier into d(pooled). No weight gradient is
-        computed. Returns (dpooled, dseq) for `backward_encoder`."""
-        cfg = self.cfg
-        H, S, half = cfg.hidden_size, cfg.max_position_embeddings, cfg.half_length
-        B, T = sv["B"], sv["Th"]
-        cap_rows, cap = B * S, B * half
-        st = hip.stream_ptr()
-        f, wt = self.P.view, self.P.wt
-        dseq = self.buf("b.dseq", (cap_rows, H))
-        if heads:
-            dt = self.buf("b.dt", (cap_rows, H))[:T]
-            dt.zero_()
-            for wname, N, h in heads:
-                npad = pad128(N)
-                dhs = self.buf("b.dhs32", (cap, H), F32)
-                dhs.zero_()
-                self.gemm(h["dl"], wt[wname], dhs, cap, H, npad, flags=hip.EPI_OUT_F32_ATOMIC,
-                          split_k=max(1, min(16, npad // 2048)), m_dev=h["cnt"])
-                hip.call("stonk_scatter_rows_f32_to_bf16", dhs.data_ptr(), H, h["rows"].data_ptr(), h["cnt"].data_ptr(),
-                         dt.data_ptr(), H, H, st)
-            dgt = self.buf("b.dgt", (cap_rows, H))
-            self.ln_bwd(dt, sv["gt"], sv["stt"][0], sv["stt"][1], f("cls.predictions.transform.LayerNorm.weight"), dgt, None,
-                        None, None, T, H, 0, 0.0, 0, 0.0, 0)
-            dut = self.buf("b.dut", (cap_rows, H))
-            hip.call("stonk_gelu_bwd_bf16", dgt.data_ptr(), sv["ut"].data_ptr(), dut.data_ptr(), T * H, st)
-            self.gemm(dut, wt["cls.predictions.transform.dense.weight"], dseq, T, H, H, kernel=self._kernel("dgrad_head", True))
-        else:
-            dseq[:T].zero_()
-        dpooled = self.buf("b.dpooled", (B, H), F32)
-        if dnsp is not None:
-            dW, db = self._scratch_wgrad(2, H)
-            hip.call("stonk_small_linear_bwd", dnsp.data_ptr(), 0, sv["pooled"].data_ptr(), H,
-                     f("cls.seq_relationship.weight").data_ptr(), dW.data_ptr(), db.data_ptr(), dpooled.data_ptr(), 0, 0, B,
-                     2, H, hip.SMALL_X_F32, st)
-        else:
-            dpooled.zero_()
-        return dpooled, dseq
-
     def input_gradients(self, input_ids, attention_mask, token_type_ids, grad_x_input, grad_norm, grad_out=None, *,
                         num_labels: Optional[int] = None, target=None, labels: Optional[dict] = None):
         """d F / d inputs_embeds per position, reduced by stonk_input_attribution into `grad_x_input` / `grad_norm` (fp32
@@ -1140,7 +1142,6 @@ class Engine:
         H, S, half = cfg.hidden_size, cfg.max_position_embeddings, cfg.half_length
         B = input_ids.shape[0]
         st = hip.stream_ptr()
-        f = self.P.view
         counts = {}
         if num_labels is None:
             given = {k: v for k, v in (labels or {}).items() if v is not None}
@@ -1150,79 +1151,124 @@ class Engine:
             counts = {k: c for k, c in zip(given, n) if c > 0}
             if not counts:
                 raise ValueError("labels: every given label is -100 - there is no prediction to attribute")
-            mlm = given["masked_lm_labels"] if "masked_lm_labels" in counts else None
-            elm = given["ent_masked_lm_labels"] if "ent_masked_lm_labels" in counts else None
-        held = (self.seed_base, self._prefetch, self.next_input_ids, list(self.rows_executed))
-        self._prefetch = self.next_input_ids = None
-        if held[1] is not None:   # (the inline backbone forward shares the prefetch's scratch buffers)
-            torch.cuda.current_stream().wait_event(held[1]["done"])
-        self._inputs_only = True
-        try:
+            # per decoder: its labels, or None for a head that is not run
+            dec_labels = [given[d.label_key] if d.label_key in counts else None for d in decoders(cfg)]
+        with self._detached(restore_rows=True, inputs_only=True):
             save: dict = {}
             out: dict = {}
             # (encode orders the stream behind the optimizer's last parameter write before it reads a trainable weight)
             if num_labels is not None:
-                seq_out, pooled = self.encode(input_ids, attention_mask, token_type_ids, False, save, (None, None))
-                logits = self.buf("ia.logits", (B, num_labels), F32)
-                hip.call("stonk_small_linear_fwd", pooled.data_ptr(), H, f("classifier.weight").data_ptr(),
-                         f("classifier.bias").data_ptr(), logits.data_ptr(), B, num_labels, H, hip.SMALL_X_F32, st)
+                _, pooled, L = self.encode(input_ids, attention_mask, token_type_ids, False, save, (None, None))
+                logits = self._pooled_linear("classifier", "ia.logits", pooled, B, num_labels)
                 if target is None:
                     target = logits.argmax(dim=1)
                 dl = self.buf("ia.dl", (B, num_labels), F32)
                 dl.zero_()
                 dl.scatter_(1, target.view(B, 1), 1.0)
-                dpooled = self.buf("b.dpooled", (B, H), F32)
-                dW, db = self._scratch_wgrad(num_labels, H)
-                hip.call("stonk_small_linear_bwd", dl.data_ptr(), 0, pooled.data_ptr(), H, f("classifier.weight").data_ptr(),
-                         dW.data_ptr(), db.data_ptr(), dpooled.data_ptr(), 0, 0, B, num_labels, H, hip.SMALL_X_F32, st)
-                dseq = self.buf("b.dseq", (B * S, H))
-                dseq[:save["Th"]].zero_()   # only position 0 of every sequence receives a gradient (from the pooler)
+                dpooled = self._pooled_linear_bwd("classifier", dl, pooled, B, num_labels)
+                dseq = self._zero_rows("b.dseq", L)   # only position 0 of a sequence receives a gradient (from the pooler)
                 out.update(logits=logits, target=target)
             else:
-                seq_out, pooled = self.encode(input_ids, attention_mask, token_type_ids, False, save, (mlm, elm))
-                T, head_map = save["Th"], save["head_map"]
-                if mlm is not None or elm is not None:
-                    nsp, gt, ut, t, stt = self._head_transform("h", seq_out, pooled, T, B, True)
-                    save.update(gt=gt, ut=ut, t=t, stt=stt)
+                seq_out, pooled, L = self.encode(input_ids, attention_mask, token_type_ids, False, save, tuple(dec_labels))
+                if any(lab is not None for lab in dec_labels):
+                    nsp, ht = self._head_transform("h", seq_out, pooled, L, True)
+                    save.update(ht)
+                    t = ht["t"]
                 else:   # NSP labels alone: no decoder runs, so neither does the head transform
                     t = None
-                    nsp = self.buf("h.nsp", (B, 2), F32)
-                    hip.call("stonk_small_linear_fwd", pooled.data_ptr(), H, f("cls.seq_relationship.weight").data_ptr(),
-                             f("cls.seq_relationship.bias").data_ptr(), nsp.data_ptr(), B, 2, H, hip.SMALL_X_F32, st)
+                    nsp = self._pooled_linear("cls.seq_relationship", "h.nsp", pooled, B, 2)
                 acc = self.buf("l.acc", (8,), F32)   # [text_sum, ent_sum, nsp_sum, nsp_cnt, -]
                 acc.zero_()
                 cnts = self.buf("l.cnt", (2,), I32)
                 heads = []
-                for hi, (nm, key, wname, N, off, lab) in enumerate((
-                        ("text", "masked_lm_labels", "cls.predictions.text_decoder.weight", cfg.vocab_size, 0, mlm),
-                        ("ent", "ent_masked_lm_labels", "cls.predictions.entity_decoder.weight", cfg.kg_vocab_size, half, elm))):
+                for hi, (dec, lab) in enumerate(zip(decoders(cfg), dec_labels)):
                     if lab is None:
                         continue
                     # (softmax - onehot) * grad_scale / count with grad_scale = -count: onehot - softmax, d log p / d logits
-                    rows, tg, cnt, hs, _, dl = self._sparse_head("l", nm, wname, N, off, lab, t, head_map, cnts[hi:hi + 1],
-                                                                 acc[hi:hi + 1], B, True, grad_scale=-float(counts[key]))
-                    heads.append((wname, N, dict(rows=rows, cnt=cnt, dl=dl)))
+                    h = self._sparse_head("l", dec, lab, t, L.head_map, cnts[hi:hi + 1], acc[hi:hi + 1], B, True,
+                                          grad_scale=-float(counts[dec.label_key]))
+                    heads.append((dec, h))
                 dnsp = None
                 if "next_sentence_labels" in counts:
                     dnsp = self.buf("l.dnsp", (B, 2), F32)
                     hip.call("stonk_nsp_xent_fwd_bwd", nsp.data_ptr(), given["next_sentence_labels"].data_ptr(), B, 2,
                              acc[2:4].data_ptr(), dnsp.data_ptr(), -float(counts["next_sentence_labels"]),
                              self.err.data_ptr(), st)
-                dpooled, dseq = self._attribution_heads(save, heads, dnsp)
+                # the backward: the training chain's pieces with the default split-K decoder dgrad; without a decoder
+                # d(sequence_output) is zero, without NSP labels so is d(pooled)
+                if heads:
+                    dt = self._zero_rows("b.dt", L)
+                    for dec, h in heads:
+                        self._decoder_dgrad(dec, h, dt, B, B * half)
+                    dseq = self._head_transform_bwd(save, dt)
+                else:
+                    dseq = self._zero_rows("b.dseq", L)
+                if dnsp is not None:
+                    dpooled = self._pooled_linear_bwd("cls.seq_relationship", dnsp, pooled, B, 2)
+                else:
+                    dpooled = self.buf("b.dpooled", (B, H), F32)
+                    dpooled.zero_()
                 out.update(score=-acc[0:3].sum())
             dsum = self.backward_encoder(dpooled, dseq, save, None)
-            plan = save["plan"]
             hip.call("stonk_input_attribution", dsum.data_ptr(), dsum.stride(0), input_ids.data_ptr(),
                      save["text_hidden"].data_ptr(), self.kg_table.data_ptr(), self.kg_table.shape[0],
-                     0 if plan is None else plan["row_of_pos"].data_ptr(), 1.0, hip.ptr(grad_x_input), hip.ptr(grad_norm),
-                     hip.ptr(grad_out), H, B, S, half, H, st)
-        finally:
-            self._inputs_only = False
-            self.seed_base, self._prefetch, self.next_input_ids = held[:3]
-            self.rows_executed[:] = held[3]
+                     hip.ptr(L.row_of_pos), 1.0, hip.ptr(grad_x_input), hip.ptr(grad_norm), hip.ptr(grad_out), H, B, S, half,
+                     H, st)
         return out
 
     # ------------------------------------------------------------------ backward
+    def _zero_rows(self, name, L: Rows):
+        """The [B * S, H] gradient buffer `name` with the rows of the sequence output cleared."""
+        x = self.buf(name, (L.B * L.S, self.cfg.hidden_size))
+        x[:L.Th].zero_()
+        return x
+
+    def _decoder_dgrad(self, dec: Decoder, h, dt, B, clear_rows, alpha: float = 1.0, wave8: bool = False) -> None:
+        """One decoder's dHs = alpha * dlogits . W over the device-side count of `h` (`_sparse_head`), scattered into the
+        head transform's output gradient `dt`. Few output tiles (count/128 x H/128), very long contraction (the
+        vocabulary): split-K into fp32, whose first `clear_rows` rows are cleared. `wave8`: the persistent 256x256 kernel
+        with 8 splits instead of 128x128 tiles with up to 16 - the caller's choice."""
+        H, cap, npad = self.cfg.hidden_size, B * self.cfg.half_length, pad128(dec.classes)
+        dhs = self.buf("b.dhs32", (cap, H), F32)
+        dhs[:clear_rows].zero_()
+        if wave8:
+            self.gemm(h["dl"], self.P.wt[dec.weight], dhs, cap, H, npad, flags=hip.EPI_OUT_F32_ATOMIC, split_k=8,
+                      m_dev=h["cnt"], alpha=alpha, kernel=hip.GEMM_WAVE8)
+        else:
+            self.gemm(h["dl"], self.P.wt[dec.weight], dhs, cap, H, npad, flags=hip.EPI_OUT_F32_ATOMIC,
+                      split_k=max(1, min(16, npad // 2048)), m_dev=h["cnt"], alpha=alpha)
+        hip.call("stonk_scatter_rows_f32_to_bf16", dhs.data_ptr(), H, h["rows"].data_ptr(), h["cnt"].data_ptr(),
+                 dt.data_ptr(), H, H, hip.stream_ptr())
+
+    def _head_transform_bwd(self, sv, dt):
+        """LayerNorm and GELU backward of the head transform, its weight gradients, and the dgrad into d(sequence_output)
+        (the "b.dseq" buffer, returned)."""
+        H = self.cfg.hidden_size
+        L = sv["layout"]
+        T, cap_rows = L.Th, L.B * L.S
+        f, g_ = self.P.view, self.P.grad_view
+        dgt = self.buf("b.dgt", (cap_rows, H))
+        self.ln_bwd(dt, sv["gt"], sv["stt"][0], sv["stt"][1], f("cls.predictions.transform.LayerNorm.weight"), dgt, None,
+                    g_("cls.predictions.transform.LayerNorm.weight"), g_("cls.predictions.transform.LayerNorm.bias"), T, H, 0,
+                    0.0, 0, 0.0, 0)
+        dut = self.buf("b.dut", (cap_rows, H))
+        hip.call("stonk_gelu_bwd_bf16", dgt.data_ptr(), sv["ut"].data_ptr(), dut.data_ptr(), T * H, hip.stream_ptr())
+        self.wgrad(dut, sv["seq_out"], g_("cls.predictions.transform.dense.weight"),
+                   g_("cls.predictions.transform.dense.bias"), H, H, T)
+        dseq = self.buf("b.dseq", (cap_rows, H))
+        self.gemm(dut, self.P.wt["cls.predictions.transform.dense.weight"], dseq, T, H, H,
+                  kernel=self._kernel("dgrad_head", True))
+        return dseq
+
+    def _pooled_linear_bwd(self, name, dy, x, B, C):
+        """Backward of `_pooled_linear`: the layer's weight gradients, and d(x) (the "b.dpooled" buffer, returned)."""
+        H = self.cfg.hidden_size
+        dpooled = self.buf("b.dpooled", (B, H), F32)
+        dW, db = self._small_wgrad(name, C, H)
+        hip.call("stonk_small_linear_bwd", dy.data_ptr(), 0, x.data_ptr(), H, self.P.view(name + ".weight").data_ptr(),
+                 dW.data_ptr(), db.data_ptr(), dpooled.data_ptr(), 0, 0, B, C, H, hip.SMALL_X_F32, hip.stream_ptr())
+        return dpooled
+
     def backward(self, gscale: float = 1.0, on_segment_done: Optional[Callable[[str], None]] = None) -> None:
         """Accumulate d(loss * gscale)/d(param) into the flat gradient buffer. `on_segment_done(name)` fires as
         soon as the gradients of a contiguous region of the flat buffer are final (DP all-reduce overlap)."""
@@ -1231,65 +1277,42 @@ class Engine:
             raise RuntimeError("backward() without a training forward (labels are required)")
         self.saved = None
         cfg = self.cfg
-        H, S, half = cfg.hidden_size, cfg.max_position_embeddings, cfg.half_length
-        B = sv["B"]
-        T, cap_rows = sv["Th"], B * S               # the heads ran on the sequence output's rows
-        st = hip.stream_ptr()
-        P = self.P
-        f, g_, wt = P.view, P.grad_view, P.wt
-        cap = B * half
+        H = cfg.hidden_size
+        L = sv["layout"]
+        B = L.B
+        cap = B * cfg.half_length
         notify = self._make_notify(on_segment_done)
         # ---- decoders (label-sparse): dHs = dlogits . W ; dW += dlogits^T . Hs
-        dt = self.buf("b.dt", (cap_rows, H))[:T]
-        dt.zero_()
-        for nm, wname, N in (("ent", "cls.predictions.entity_decoder.weight", cfg.kg_vocab_size),
-                             ("text", "cls.predictions.text_decoder.weight", cfg.vocab_size)):
-            npad = pad128(N)
-            h = sv[nm]
-            # few output tiles (count/128 x H/128), very long contraction (the vocabulary): split-K into fp32
-            dhs = self.buf("b.dhs32", (cap, H), F32)
-            # (labelled rows of this head <= read rows, known to the host in the packed layout: the split-K atomics and the
-            # scatter touch no row beyond them)
-            dhs[:cap if sv["rd"] is None else min(cap, (sv["rd"]["n"] + 255) // 256 * 256)].zero_()
+        dt = self._zero_rows("b.dt", L)
+        # (labelled rows of a head <= read rows, known to the host in the packed layout: the split-K atomics and the
+        # scatter touch no row of dHs beyond them)
+        clear = cap if L.rd is None else min(cap, (L.rd.n + 255) // 256 * 256)
+        for dec in reversed(decoders(cfg)):
+            npad, h = pad128(dec.classes), sv[dec.name]
             # the persistent 256x256 kernel with 8 splits (<= 30 live tiles x 8 = one round of the CUs) against 128x128
             # tiles with 16: 734 us against 951 for the entity decoder (tools/bench_decoder_dgrad.py)
             # (not beside a running all-reduce - the entity decoder's bucket is in flight when the text decoder's dgrad is
             # launched: a persistent launch would wait for the CUs RCCL holds, tools/hog_test.py)
             # (the written-out four-wave kernel on 256x192 tiles is the slower one here: DESIGN.md section 4.3)
-            if npad >= 16384 and cap >= 1024 and H % 256 == 0 and not (self.comm_overlap and nm != "ent"):
-                self.gemm(h["dl"], wt[wname], dhs, cap, H, npad, flags=hip.EPI_OUT_F32_ATOMIC, split_k=8, m_dev=h["cnt"],
-                          alpha=gscale, kernel=hip.GEMM_WAVE8)
-            else:
-                self.gemm(h["dl"], wt[wname], dhs, cap, H, npad, flags=hip.EPI_OUT_F32_ATOMIC,
-                          split_k=max(1, min(16, npad // 2048)), m_dev=h["cnt"], alpha=gscale)
-            hip.call("stonk_scatter_rows_f32_to_bf16", dhs.data_ptr(), H, h["rows"].data_ptr(), h["cnt"].data_ptr(),
-                     dt.data_ptr(), H, H, st)
-            self.wgrad(h["dl"], h["hs"], g_(wname, padded=True), None, npad, H, cap, k_dev=h["cnt"], alpha=gscale, name=wname)
-            notify(wname)
+            wave8 = npad >= 16384 and cap >= 1024 and H % 256 == 0 and not (self.comm_overlap and dec.name != "ent")
+            self._decoder_dgrad(dec, h, dt, B, clear, alpha=gscale, wave8=wave8)
+            self.wgrad(h["dl"], h["hs"], self.P.grad_view(dec.weight, padded=True), None, npad, H, cap, k_dev=h["cnt"],
+                       alpha=gscale, name=dec.weight)
+            notify(dec.weight)
         # ---- head transform backward
-        dgt = self.buf("b.dgt", (cap_rows, H))
-        self.ln_bwd(dt, sv["gt"], sv["stt"][0], sv["stt"][1], f("cls.predictions.transform.LayerNorm.weight"), dgt, None,
-                    g_("cls.predictions.transform.LayerNorm.weight"), g_("cls.predictions.transform.LayerNorm.bias"), T, H, 0,
-                    0.0, 0, 0.0, 0)
-        dut = self.buf("b.dut", (cap_rows, H))
-        hip.call("stonk_gelu_bwd_bf16", dgt.data_ptr(), sv["ut"].data_ptr(), dut.data_ptr(), T * H, st)
-        self.wgrad(dut, sv["seq_out"], g_("cls.predictions.transform.dense.weight"),
-                   g_("cls.predictions.transform.dense.bias"), H, H, T)
-        dseq = self.buf("b.dseq", (cap_rows, H))
-        self.gemm(dut, wt["cls.predictions.transform.dense.weight"], dseq, T, H, H, kernel=self._kernel("dgrad_head", True))
+        dseq = self._head_transform_bwd(sv, dt)
         # ---- NSP + pooler (fp32), pooler gradient lands on position 0 of d(sequence_output)
         dnsp = sv["dnsp"]
         if gscale != 1.0:
-            hip.call("stonk_scale_f32", dnsp.data_ptr(), dnsp.numel(), gscale, st)
-        dpooled = self.buf("b.dpooled", (B, H), F32)
-        hip.call("stonk_small_linear_bwd", dnsp.data_ptr(), 0, sv["pooled"].data_ptr(), H,
-                 f("cls.seq_relationship.weight").data_ptr(), g_("cls.seq_relationship.weight").data_ptr(),
-                 g_("cls.seq_relationship.bias").data_ptr(), dpooled.data_ptr(), 0, 0, B, 2, H, hip.SMALL_X_F32, st)
+            hip.call("stonk_scale_f32", dnsp.data_ptr(), dnsp.numel(), gscale, hip.stream_ptr())
+        dpooled = self._pooled_linear_bwd("cls.seq_relationship", dnsp, sv["pooled"], B, 2)
         self.backward_encoder(dpooled, dseq, sv, notify)
 
-    def _scratch_wgrad(self, N: int, K: int):
-        """(inputs-only backward) somewhere for stonk_small_linear_bwd to put the dW [N, K] / db [N] it cannot be told to
-        skip: one scratch buffer, never read."""
+    def _small_wgrad(self, name: str, N: int, K: int):
+        """(dW [N, K], db [N]) for stonk_small_linear_bwd of the linear layer `name`: its gradient views - in the
+        inputs-only backward one scratch buffer, never read, because the kernel cannot be told to skip them."""
+        if not self._inputs_only:
+            return self.P.grad_view(name + ".weight"), self.P.grad_view(name + ".bias")
         w = self.buf("ia.dw", (N * K + N,), F32)
         return w[:N * K], w[N * K:]
 
@@ -1322,40 +1345,37 @@ class Engine:
             notify = lambda name: None   # noqa: E731
         cfg = self.cfg
         H, S = cfg.hidden_size, cfg.max_position_embeddings
-        B = sv["B"]
-        T, rows, plan, rd, first_rows = sv["T"], sv["rows"], sv["plan"], sv["rd"], sv["first_rows"]
+        L = sv["layout"]
+        B, T = L.B, L.T
         cap = B * S
         st = hip.stream_ptr()
         f, g_ = self.P.view, self.P.grad_view
-        if plan is None:
+        if not L.packed:
             acc, ld_acc = dseq, S * H
         else:   # packed: position 0 of sequence b is row first_rows[b] - its gradient rows are gathered, added to, scattered back
             nb = self.buf("e.nb", (1,), I32)
             nb.fill_(B)
             acc, ld_acc = self.buf("b.dfirst", ((B + 127) // 128 * 128, H)), H
-            self._gather_rows(dseq, first_rows, nb, acc, acc.shape[0])
-        dWp, dbp = (g_("bert.pooler.dense.weight"), g_("bert.pooler.dense.bias")) if not self._inputs_only \
-            else self._scratch_wgrad(H, H)
+            self._gather_rows(dseq, L.first_rows, nb, acc, acc.shape[0])
+        dWp, dbp = self._small_wgrad("bert.pooler.dense", H, H)
         hip.call("stonk_small_linear_bwd", dpooled.data_ptr(), sv["pooled"].data_ptr(), sv["first"].data_ptr(),
                  sv["ld_first"], f("bert.pooler.dense.weight").data_ptr(), dWp.data_ptr(), dbp.data_ptr(), 0,
                  acc.data_ptr(), ld_acc, B, H, H, hip.SMALL_TANH, st)
-        if plan is not None:
-            hip.call("stonk_scatter_rows_bf16", acc.data_ptr(), H, first_rows.data_ptr(), nb.data_ptr(), dseq.data_ptr(), H,
-                     H, st)
+        if L.packed:
+            hip.call("stonk_scatter_rows_bf16", acc.data_ptr(), H, L.first_rows.data_ptr(), nb.data_ptr(), dseq.data_ptr(),
+                     H, H, st)
         notify("bert.pooler.dense.bias")
         # ---- encoder layers, last to first
         dy = dseq
-        cu = None if plan is None else plan["cu"]
         last = cfg.num_hidden_layers - 1
-        if plan is not None and rows < T:   # what an earlier step left in the rows no sequence owns must not reach dW
+        if L.packed and L.rows < T:   # what an earlier step left in the rows no sequence owns must not reach dW
             for par in (0, 1):
-                self.buf(f"b.dqkv.{par}", (cap, 3 * H))[rows:T].zero_()
+                self.buf(f"b.dqkv.{par}", (cap, 3 * H))[L.rows:T].zero_()
         span = self._span_begin()
         for i in reversed(range(cfg.num_hidden_layers)):
             prefix = f"bert.encoder.layer.{i}"
             with self.block(f"K15 encoder layer {i} bwd"):
-                dy = self.layer_bwd(prefix, dy, B, S, sv["attention_mask"], sv["p_hid"], sv["p_att"], i, sv[prefix], T=T,
-                                    cu=cu, rows=rows, rd=rd if i == last else None)
+                dy = self.layer_bwd(prefix, dy, L, sv["p_hid"], sv["p_att"], i, sv[prefix], last=i == last)
             notify(prefix)
         if span is not None and self._wstream is not None:   # (timing only) the span ends when the layers' weight gradients have
             torch.cuda.current_stream().wait_stream(self._wstream)
@@ -1370,7 +1390,7 @@ class Engine:
             hip.call("stonk_embed_grad", dsum.data_ptr(), hip.ptr(sv["token_type_ids"]),
                      g_("bert.embeddings.position_embeddings.weight").data_ptr(),
                      g_("bert.embeddings.token_type_embeddings.weight").data_ptr(), B, S, H, cfg.type_vocab_size,
-                     0 if plan is None else plan["row_of_pos"].data_ptr(), st)
+                     hip.ptr(L.row_of_pos), st)
             self._word_embed_grad(dsum, sv)
         notify("bert.embeddings")
         self.mark("backward_end")
@@ -1391,20 +1411,17 @@ class Engine:
         H = cfg.hidden_size
         B = input_ids.shape[0]
         st = hip.stream_ptr()
-        f = self.P.view
         save: dict = {}
         # (the classification head hands out no per-position output: the encoder runs on the packed rows, training or not)
-        seq_out, pooled = self.encode(input_ids, attention_mask, token_type_ids, training, save, (None, None))
+        seq_out, pooled, L = self.encode(input_ids, attention_mask, token_type_ids, training, save, (None, None))
         p = cfg.hidden_dropout_prob if training else 0.0
         dropped = pooled
         if p > 0:
             dropped = self.buf("c.dropped", (B, H), F32)
             hip.call("stonk_dropout_f32", pooled.data_ptr(), dropped.data_ptr(), B * H, p, self.seed(300, 0), st)
-        logits = self.buf("c.logits", (B, num_labels), F32)
-        hip.call("stonk_small_linear_fwd", dropped.data_ptr(), H, f("classifier.weight").data_ptr(),
-                 f("classifier.bias").data_ptr(), logits.data_ptr(), B, num_labels, H, hip.SMALL_X_F32, st)
+        logits = self._pooled_linear("classifier", "c.logits", dropped, B, num_labels)
         out = dict(logits=logits, pooler_output=pooled,
-                   hidden_states=seq_out.view(B, cfg.max_position_embeddings, H) if save["plan"] is None else None)
+                   hidden_states=None if L.packed else seq_out.view(B, cfg.max_position_embeddings, H))
         if labels is not None:
             dl = self.buf("c.dl", (B, num_labels), F32) if need_backward else None
             loss = self.buf("c.loss", (1,), F32)
@@ -1428,24 +1445,18 @@ class Engine:
         if sv is None:
             raise RuntimeError("backward_cls() without a training forward (labels are required)")
         self.saved = None
-        cfg = self.cfg
-        H, S = cfg.hidden_size, cfg.max_position_embeddings
-        B, C = sv["B"], sv["num_labels"]
+        L = sv["layout"]
+        B, H = L.B, self.cfg.hidden_size
         st = hip.stream_ptr()
-        f, g_ = self.P.view, self.P.grad_view
         notify = self._make_notify(on_segment_done)
         dl = sv["dl"]
         if gscale != 1.0:
             hip.call("stonk_scale_f32", dl.data_ptr(), dl.numel(), gscale, st)
-        dpooled = self.buf("b.dpooled", (B, H), F32)
-        hip.call("stonk_small_linear_bwd", dl.data_ptr(), 0, sv["dropped"].data_ptr(), H, f("classifier.weight").data_ptr(),
-                 g_("classifier.weight").data_ptr(), g_("classifier.bias").data_ptr(), dpooled.data_ptr(), 0, 0, B, C, H,
-                 hip.SMALL_X_F32, st)
+        dpooled = self._pooled_linear_bwd("classifier", dl, sv["dropped"], B, sv["num_labels"])
         if sv["p_cls"] > 0:  # same (seed, index) mask as the forward
             hip.call("stonk_dropout_f32", dpooled.data_ptr(), dpooled.data_ptr(), B * H, sv["p_cls"], self.seed(300, 0), st)
         notify("classifier.bias")
-        dseq = self.buf("b.dseq", (B * S, H))
-        dseq[:sv["Th"]].zero_()  # only position 0 of every sequence receives a gradient (from the pooler)
+        dseq = self._zero_rows("b.dseq", L)  # only position 0 of every sequence receives a gradient (from the pooler)
         self.backward_encoder(dpooled, dseq, sv, notify)
 
 
@@ -1480,9 +1491,8 @@ class TextEngine(Engine):
         return self.kg_table, None
 
     def _word_embed_grad(self, dsum, sv) -> None:
-        cfg, plan = self.cfg, sv["plan"]
+        cfg, L = self.cfg, sv["layout"]
         dword = self.P.grad_view(self.WORD)
         hip.call("stonk_word_embed_grad", dsum.data_ptr(), dsum.stride(0), sv["input_ids"].data_ptr(),
-                 0 if plan is None else plan["row_of_pos"].data_ptr(), dword.data_ptr(), dword.stride(0), cfg.vocab_size,
-                 self.PADDING_IDX, sv["B"], cfg.max_position_embeddings, cfg.hidden_size, self.err.data_ptr(),
-                 hip.stream_ptr())
+                 hip.ptr(L.row_of_pos), dword.data_ptr(), dword.stride(0), cfg.vocab_size, self.PADDING_IDX, L.B,
+                 cfg.max_position_embeddings, cfg.hidden_size, self.err.data_ptr(), hip.stream_ptr())

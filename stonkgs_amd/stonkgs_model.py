@@ -314,8 +314,8 @@ class STonKGsForPreTraining(FlatBufferModel):
         if input_ids.dim() != 2 or input_ids.shape[1] != cfg.max_position_embeddings:
             raise ValueError(f"input_ids must be [B, {cfg.max_position_embeddings}] (text half | entity half)")
         self._sync_derived()
-        seq_out, pooled = self.engine.encode(input_ids, attention_mask, token_type_ids, False, None,
-                                             (None, None) if pooled_only else None)
+        seq_out, pooled, _ = self.engine.encode(input_ids, attention_mask, token_type_ids, False, None,
+                                                (None, None) if pooled_only else None)
         self.engine.check_errors()
         B = input_ids.shape[0]
         if pooled_only:

@@ -22,6 +22,7 @@ import torch
 
 from . import _hip as hip
 from .data import collate, synthetic_batch
+from .engine import decoders
 from .flat_model import _load_weights_file, as_long
 from .params import FlatStore
 
@@ -434,7 +435,7 @@ def segment_ends_for(model) -> Dict[str, int]:
     seg = {}
     if "classifier.bias" in store.index:
         seg["classifier.bias"] = store.span("classifier.bias")[1]
-    for name in ("cls.predictions.entity_decoder.weight", "cls.predictions.text_decoder.weight", "bert.pooler.dense.bias"):
+    for name in [d.weight for d in reversed(decoders(cfg))] + ["bert.pooler.dense.bias"]:
         if name in store.index:
             seg[name] = store.span(name)[1]
     for i in range(cfg.num_hidden_layers):
@@ -483,8 +484,7 @@ class Trainer:
         # A sharded optimizer updates pieces of buckets and zeroes the whole gradient buffer: it keeps the flat path.
         self._keep_grad = None
         if not self.sync.shard:
-            names = [n for n in ("cls.predictions.entity_decoder.weight", "cls.predictions.text_decoder.weight")
-                     if n in model._store.index]
+            names = [d.weight for d in reversed(decoders(model.config)) if d.weight in model._store.index]
             if names:
                 model.engine.store_names = tuple(names)
                 spans = sorted(model._store.span(n) for n in names)

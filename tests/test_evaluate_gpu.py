@@ -256,6 +256,56 @@ def test_evaluation_is_invisible_to_training(g2):
     assert float((diff > 2e-6).float().mean()) < 2e-3
 
 
+@pytest.mark.parametrize("call", ["evaluate", "attention_maps", "attributions_labels", "attributions_target"])
+def test_a_failing_detached_call_puts_the_training_state_back(g2, call, monkeypatch):
+    """The exception path of Engine._detached: with a prefetched backbone forward waiting and the hint for the next one
+    set, the body fails in its first layer (Engine.layer_fwd is made to raise: host logic only, nothing runs that was not
+    asked for). The call raises, and the dropout counter, the inputs-only flag, the prefetch, the hint, `saved` and - for
+    the callers that restore it - `rows_executed` are what they were."""
+    from stonkgs_amd.engine import Engine
+    from tests.test_finetune_gpu import _build_cls
+
+    batch = g2["batch"]
+    inputs = {k: batch[k] for k in ("input_ids", "attention_mask", "token_type_ids")}
+    model = g2["model"]
+    if call == "attributions_target":
+        sd = dict(g2["sd"])
+        sd["classifier.weight"], sd["classifier.bias"] = torch.zeros(3, g2["cfg"].hidden_size), torch.zeros(3)
+        model = _build_cls(g2["cfg"], sd, g2["tsv_rows"], 3)
+    model.eval()
+    eng = model.engine
+    ids = batch["input_ids"].to(model.device)
+    try:
+        eng.prefetch_backbone(ids, False)
+        eng.next_input_ids = ids
+        before = (eng.seed_base, eng._inputs_only, eng._prefetch, eng.next_input_ids, list(eng.rows_executed))
+        assert before[2] is not None and eng.saved is None
+
+        def fail(*args, **kwargs):
+            raise RuntimeError("layer_fwd was made to fail")
+
+        monkeypatch.setattr(Engine, "layer_fwd", fail)
+        with pytest.raises(RuntimeError, match="made to fail"):
+            if call == "evaluate":
+                model.evaluate_batch(batch, k=10)
+            elif call == "attention_maps":
+                model.attention_maps(**inputs, layers=[0])
+            elif call == "attributions_labels":
+                model.input_attributions(**inputs, labels={k: batch[k] for k in ("masked_lm_labels", "ent_masked_lm_labels",
+                                                                                "next_sentence_labels")})
+            else:
+                model.input_attributions(**inputs)
+        assert eng.seed_base == before[0] and eng._inputs_only == before[1]
+        assert eng._prefetch is before[2] and eng.next_input_ids is before[3]
+        if call != "attention_maps":   # (a successful attention_maps counts its rows: nothing to put back)
+            assert list(eng.rows_executed) == before[4]
+        assert eng.saved is None
+    finally:   # the model is the module's: leave no prefetch behind
+        monkeypatch.undo()
+        torch.cuda.synchronize()
+        eng._prefetch = eng.next_input_ids = None
+
+
 def test_train_evaluates_every_eval_steps(g2):
     """TrainingArguments.eval_steps: during train() the evaluation result is appended to log_history with the step, every
     eval_steps optimizer steps, and the module is in training mode afterwards."""
