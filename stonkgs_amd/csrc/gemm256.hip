@@ -59,11 +59,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const GemmArgs p) {
   }
   const int N = p.N;
   const int ntm = (M + BM - 1) / BM, ntn = (N + BN - 1) / BN;
-  int nk_total = TN ? (p.K + BK - 1) / BK : p.K / BK;
-  if (p.k_dev) {
-    const int kd = (*p.k_dev + BK - 1) / BK;
-    nk_total = kd < nk_total ? kd : nk_total;
-  }
+  const int nk_total = live_count(p.k_dev, TN ? (p.K + BK - 1) / BK : p.K / BK, BK);
   const int nk_per = (nk_total + p.split_k - 1) / p.split_k;
   const int per_split = ntm * ntn;
   const int total = per_split * p.split_k;
@@ -87,16 +83,9 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const GemmArgs p) {
     }
     const int ks = idx / per_split;
     const int tt = idx - ks * per_split;
-    int rt, ct;
-    if (ntm >= ntn) {
-      rt = tt / ntn;
-      ct = tt - rt * ntn;
-    } else {
-      ct = tt / ntm;
-      rt = tt - ct * ntm;
-    }
-    o.m0 = rt * BM;
-    o.n0 = ct * BN;
+    const TileRC t = tile_split(tt, ntm, ntn);
+    o.m0 = t.rt * BM;
+    o.n0 = t.ct * BN;
     o.k_begin = (long)ks * nk_per * BK;
     int nk = nk_total - ks * nk_per;
     o.nk = nk < nk_per ? nk : nk_per;
@@ -566,16 +555,7 @@ int stonk_gemm256_launch(const GemmArgs& a, int out_mode, hipStream_t st) {
   if (out_mode == 1) return epi == 0 ? launch256<1, 0>(a, grid, st) : launch256<1, -1>(a, grid, st);
   if (out_mode == 2) return launch256<2, 0>(a, grid, st);
   if (out_mode == 3) return launch256<3, 0>(a, grid, st);
-  switch (epi) {   // the combinations the STonKGs step uses are compiled with constant flags
-    case 0: return launch256<0, 0>(a, grid, st);
-    case B: return launch256<0, B>(a, grid, st);
-    case B | G: return launch256<0, B | G>(a, grid, st);
-    case B | G | SV: return launch256<0, B | G | SV>(a, grid, st);
-    case GB: return launch256<0, GB>(a, grid, st);
-    case B | G | SV | AG: return launch256<0, B | G | SV | AG>(a, grid, st);
-    case GB | AG: return launch256<0, GB | AG>(a, grid, st);
-    case R: return launch256<0, R>(a, grid, st);
-    case B | R: return launch256<0, B | R>(a, grid, st);
-    default: return launch256<0, -1>(a, grid, st);
-  }
+  // the combinations the STonKGs step uses are compiled with constant flags
+  if (!EpisWave8::has(epi)) return launch256<0, -1>(a, grid, st);
+  return epi_dispatch(EpisWave8{}, epi, STONK_ESHAPE, [&](auto e) { return launch256<0, decltype(e)::value>(a, grid, st); });
 }

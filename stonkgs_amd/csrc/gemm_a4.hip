@@ -126,11 +126,7 @@ __global__ __launch_bounds__(256, 1) void gemm_a4_kernel(const GemmArgs p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 1, wc = wave & 1;
 
-  int M = p.M;
-  if (p.m_dev) {
-    const int md = *p.m_dev;
-    M = md < M ? md : M;
-  }
+  const int M = live_count(p.m_dev, p.M);
   const int N = p.N;
   const int ntm = (M + BM - 1) / BM, ntn = (N + BN - 1) / BN;
   // K tiles per work item: all of them, or (split_k > 1: the atomic output) an even share - the last item of a tile takes
@@ -168,16 +164,9 @@ __global__ __launch_bounds__(256, 1) void gemm_a4_kernel(const GemmArgs p) {
       o.k0 = sp * per;
       o.nk = nk_all - o.k0 < per ? nk_all - o.k0 : per;
     }
-    int rt, ct;
-    if (ntm >= ntn) {
-      rt = idx / ntn;
-      ct = idx - rt * ntn;
-    } else {
-      ct = idx / ntm;
-      rt = idx - ct * ntm;
-    }
-    o.m0 = rt * BM;
-    o.n0 = ct * BN;
+    const TileRC t = tile_split(idx, ntm, ntn);
+    o.m0 = t.rt * BM;
+    o.n0 = t.ct * BN;
     return true;
   };
 
@@ -234,11 +223,7 @@ __global__ __launch_bounds__(256, 1) void gemm_a4_kernel(const GemmArgs p) {
   i32x4 curA, curB;                   // the operand cursors (s[36:39], s[40:43] inside the blocks)
   cursor_of(cw, curA, curB);
 
-#define STONK_A4_VOFF_OPERANDS                                                                                          \
-  [voffA0] "v"(voffA[0]), [voffA1] "v"(voffA[1]), [voffA2] "v"(voffA[2]), [voffA3] "v"(voffA[3]), [voffA4] "v"(voffA[4]), \
-      [voffA5] "v"(voffA[5]), [voffA6] "v"(voffA[6]), [voffA7] "v"(voffA[7]), [voffB0] "v"(voffB[0]),                   \
-      [voffB1] "v"(voffB[1]), [voffB2] "v"(voffB[2]), [voffB3] "v"(voffB[3]), [voffB4] "v"(voffB[4]),                   \
-      [voffB5] "v"(voffB[5]), [voffB6] "v"(voffB[6]), [voffB7] "v"(voffB[7]), [m0a] "s"(m0a), [m0b] "s"(m0b)
+#define STONK_A4_VOFF_OPERANDS STONK_A4_VOFF_IN(voffA, voffB), [m0a] "s"(m0a), [m0b] "s"(m0b)
 
   // K tiles 0 and 1 of the first tile
   if (BN_ == 256)
@@ -281,31 +266,16 @@ __global__ __launch_bounds__(256, 1) void gemm_a4_kernel(const GemmArgs p) {
 #define STONK_A4_TILE_OPERANDS                                                                                        \
   STONK_A4_VOFF_OPERANDS, [raA0] "v"(raA[0]), [raA1] "v"(raA[1]), [raB0] "v"(raB[0]), [raB1] "v"(raB[1]),             \
       [nal] "s"(nxA[0]), [nah] "s"(nxA[1]), [nan] "s"(nxA[2]), [nbl] "s"(nxB[0]), [nbh] "s"(nxB[1]), [nbn] "s"(nxB[2])
-#define STONK_A4_CLOBBERS                                                                                              \
-  "m0", "scc", "memory", "v128", "v129", "v130", "v131", "v132", "v133", "v134", "v135", "v136", "v137", "v138", "v139", \
-      "v140", "v141", "v142", "v143", "v144", "v145", "v146", "v147", "v148", "v149", "v150", "v151", "v152", "v153",  \
-      "v154", "v155", "v156", "v157", "v158", "v159", "v160", "v161", "v162", "v163", "v164", "v165", "v166", "v167",  \
-      "v168", "v169", "v170", "v171", "v172", "v173", "v174", "v175", "v176", "v177", "v178", "v179", "v180", "v181",  \
-      "v182", "v183", "v184", "v185", "v186", "v187", "v188", "v189", "v190", "v191", "v192", "v193", "v194", "v195",  \
-      "v196", "v197", "v198", "v199", "v200", "v201", "v202", "v203", "v204", "v205", "v206", "v207", "v208", "v209",  \
-      "v210", "v211", "v212", "v213", "v214", "v215", "v216", "v217", "v218", "v219", "v220", "v221", "v222", "v223",  \
-      "v224", "v225", "v226", "v227", "v228", "v229", "v230", "v231", "v232", "v233", "v234", "v235", "v236", "v237",  \
-      "v238", "v239", "v240", "v241", "v242", "v243", "v244", "v245", "v246", "v247", "v248", "v249", "v250", "v251",  \
-      "v252", "v253", "v254", "v255"
+#define STONK_A4_CLOBBERS "m0", "scc", "memory", STONK_A4_FRAG_CLOBBERS
     if (BN_ == 256) {
       asm volatile(STONK_A4_TILE_256
-                   : "={a[0:15]}"(acc[0]), "={a[16:31]}"(acc[1]), "={a[32:47]}"(acc[2]), "={a[48:63]}"(acc[3]),
-                     "={a[64:79]}"(acc[4]), "={a[80:95]}"(acc[5]), "={a[96:111]}"(acc[6]), "={a[112:127]}"(acc[7]),
-                     "={a[128:143]}"(acc[8]), "={a[144:159]}"(acc[9]), "={a[160:175]}"(acc[10]), "={a[176:191]}"(acc[11]),
-                     "={a[192:207]}"(acc[12]), "={a[208:223]}"(acc[13]), "={a[224:239]}"(acc[14]), "={a[240:255]}"(acc[15]),
+                   : STONK_A4_ACC_OUT_16(acc),
                      "+{s[36:39]}"(curA), "+{s[40:43]}"(curB), [rem] "+s"(rem)
                    : STONK_A4_TILE_OPERANDS
                    : STONK_A4_CLOBBERS);
     } else {
       asm volatile(STONK_A4_TILE_192
-                   : "={a[0:15]}"(acc[0]), "={a[16:31]}"(acc[1]), "={a[32:47]}"(acc[2]), "={a[48:63]}"(acc[3]),
-                     "={a[64:79]}"(acc[4]), "={a[80:95]}"(acc[5]), "={a[96:111]}"(acc[6]), "={a[112:127]}"(acc[7]),
-                     "={a[128:143]}"(acc[8]), "={a[144:159]}"(acc[9]), "={a[160:175]}"(acc[10]), "={a[176:191]}"(acc[11]),
+                   : STONK_A4_ACC_OUT_12(acc),
                      "+{s[36:39]}"(curA), "+{s[40:43]}"(curB), [rem] "+s"(rem)
                    : STONK_A4_TILE_OPERANDS
                    : STONK_A4_CLOBBERS);
@@ -357,29 +327,11 @@ __global__ __launch_bounds__(256, 1) void gemm_a4_kernel(const GemmArgs p) {
           ys[jp][e] = acc[by >> 2][4 * (by & 3) + e];
         }
       }
-#define STONK_A4_SWAP4(a, b) \
-  "v_permlane16_swap_b32 %" #a ", %" #b "\n"
-      if (NJP == 4) {
-        asm volatile("s_nop 1\n" STONK_A4_SWAP4(0, 16) STONK_A4_SWAP4(1, 17) STONK_A4_SWAP4(2, 18) STONK_A4_SWAP4(3, 19)
-                     STONK_A4_SWAP4(4, 20) STONK_A4_SWAP4(5, 21) STONK_A4_SWAP4(6, 22) STONK_A4_SWAP4(7, 23)
-                     STONK_A4_SWAP4(8, 24) STONK_A4_SWAP4(9, 25) STONK_A4_SWAP4(10, 26) STONK_A4_SWAP4(11, 27)
-                     STONK_A4_SWAP4(12, 28) STONK_A4_SWAP4(13, 29) STONK_A4_SWAP4(14, 30) STONK_A4_SWAP4(15, 31) "s_nop 1"
-                     : "+v"(xs[0][0]), "+v"(xs[0][1]), "+v"(xs[0][2]), "+v"(xs[0][3]), "+v"(xs[1][0]), "+v"(xs[1][1]),
-                       "+v"(xs[1][2]), "+v"(xs[1][3]), "+v"(xs[2][0]), "+v"(xs[2][1]), "+v"(xs[2][2]), "+v"(xs[2][3]),
-                       "+v"(xs[NJP - 1][0]), "+v"(xs[NJP - 1][1]), "+v"(xs[NJP - 1][2]), "+v"(xs[NJP - 1][3]),
-                       "+v"(ys[0][0]), "+v"(ys[0][1]), "+v"(ys[0][2]), "+v"(ys[0][3]), "+v"(ys[1][0]), "+v"(ys[1][1]),
-                       "+v"(ys[1][2]), "+v"(ys[1][3]), "+v"(ys[2][0]), "+v"(ys[2][1]), "+v"(ys[2][2]), "+v"(ys[2][3]),
-                       "+v"(ys[NJP - 1][0]), "+v"(ys[NJP - 1][1]), "+v"(ys[NJP - 1][2]), "+v"(ys[NJP - 1][3]));
+      if constexpr (NJP == 4) {
+        asm volatile(STONK_A4_SWAP_4(xs, ys));
       } else {
-        asm volatile("s_nop 1\n" STONK_A4_SWAP4(0, 12) STONK_A4_SWAP4(1, 13) STONK_A4_SWAP4(2, 14) STONK_A4_SWAP4(3, 15)
-                     STONK_A4_SWAP4(4, 16) STONK_A4_SWAP4(5, 17) STONK_A4_SWAP4(6, 18) STONK_A4_SWAP4(7, 19)
-                     STONK_A4_SWAP4(8, 20) STONK_A4_SWAP4(9, 21) STONK_A4_SWAP4(10, 22) STONK_A4_SWAP4(11, 23) "s_nop 1"
-                     : "+v"(xs[0][0]), "+v"(xs[0][1]), "+v"(xs[0][2]), "+v"(xs[0][3]), "+v"(xs[1][0]), "+v"(xs[1][1]),
-                       "+v"(xs[1][2]), "+v"(xs[1][3]), "+v"(xs[2][0]), "+v"(xs[2][1]), "+v"(xs[2][2]), "+v"(xs[2][3]),
-                       "+v"(ys[0][0]), "+v"(ys[0][1]), "+v"(ys[0][2]), "+v"(ys[0][3]), "+v"(ys[1][0]), "+v"(ys[1][1]),
-                       "+v"(ys[1][2]), "+v"(ys[1][3]), "+v"(ys[2][0]), "+v"(ys[2][1]), "+v"(ys[2][2]), "+v"(ys[2][3]));
+        asm volatile(STONK_A4_SWAP_3(xs, ys));
       }
-#undef STONK_A4_SWAP4
 #pragma unroll
       for (int jp = 0; jp < NJP; ++jp) {
         float v[8] = {xs[jp][0], xs[jp][1], xs[jp][2], xs[jp][3], ys[jp][0], ys[jp][1], ys[jp][2], ys[jp][3]};
@@ -438,17 +390,16 @@ int launch_a4(const GemmArgs& a, int grid, hipStream_t st) {
 }  // namespace
 
 // Is there an instance of the kernel for this epilogue (flags & epi_bits::MASK), output type and tile width (256 | 192)?
-// Says what the switch blocks of the launcher below list; stonk_gemm_nt_bf16 asks it before it routes a launch here. Every
-// 192-wide bf16 instance has a 256-wide twin, so for a width the launcher chooses itself the answer at 256 holds.
+// Asks the lists (gemm_common.h) that the launcher below launches through; stonk_gemm_nt_bf16 asks it before it routes a
+// launch here. Every 192-wide bf16 instance has a 256-wide twin, so for a width the launcher chooses itself the answer at
+// 256 holds.
 bool stonk_gemm_a4_has_instance(int epi, int out, int tile_n) {
   using namespace epi_bits;
   if (out == STONK_EPI_OUT_F16) return epi == 0 && tile_n == 256;
   // (the atomic form on 256 x 192 tiles only: its 256-wide instance does not fit the compiler's half of the register file)
   if (out == STONK_EPI_OUT_F32_ATOMIC) return epi == 0 && tile_n == 192;
   if (out != STONK_EPI_OUT_BF16) return false;
-  if (tile_n == 192) return epi_has_192(epi);
-  return epi == 0 || epi == B || epi == (B | G) || epi == (B | G | SV) || epi == GB || epi == (B | G | SV | AG) ||
-         epi == (GB | AG) || epi == R || epi == (B | R) || epi == (B | R | D);
+  return tile_n == 192 ? Epis192::has(epi) : EpisStep::has(epi);
 }
 
 // Launcher used by stonk_gemm_nt_bf16 (gemm_bf16.hip). Requires K % 128 == 0, ld % 64 == 0, 256 rows of every operand within
@@ -472,26 +423,7 @@ int stonk_gemm_a4_launch(const GemmArgs& a, int tile_n, int items_per_wg, hipStr
   if (!stonk_gemm_a4_has_instance(epi, out, tile_n)) return STONK_ESHAPE;
   if (out == STONK_EPI_OUT_F16) return launch_a4<STONK_EPI_OUT_F16, 256>(a, grid, st);
   if (out == STONK_EPI_OUT_F32_ATOMIC) return launch_a4<STONK_EPI_OUT_F32_ATOMIC, 192>(a, grid, st);
-  if (tile_n == 192) {
-    switch (epi) {
-      case 0: return launch_a4<0, 192>(a, grid, st);
-      case B: return launch_a4<B, 192>(a, grid, st);
-      case R: return launch_a4<R, 192>(a, grid, st);
-      case B | R: return launch_a4<B | R, 192>(a, grid, st);
-      default: return launch_a4<B | R | D, 192>(a, grid, st);
-    }
-  }
-  switch (epi) {
-    case 0: return launch_a4<0, 256>(a, grid, st);
-    case B: return launch_a4<B, 256>(a, grid, st);
-    case B | G: return launch_a4<B | G, 256>(a, grid, st);
-    case B | G | SV: return launch_a4<B | G | SV, 256>(a, grid, st);
-    case GB: return launch_a4<GB, 256>(a, grid, st);
-    case B | G | SV | AG: return launch_a4<B | G | SV | AG, 256>(a, grid, st);
-    case GB | AG: return launch_a4<GB | AG, 256>(a, grid, st);
-    case R: return launch_a4<R, 256>(a, grid, st);
-    case B | R: return launch_a4<B | R, 256>(a, grid, st);
-    case B | R | D: return launch_a4<B | R | D, 256>(a, grid, st);
-    default: return STONK_ESHAPE;
-  }
+  if (tile_n == 192)
+    return epi_dispatch(Epis192{}, epi, STONK_ESHAPE, [&](auto e) { return launch_a4<decltype(e)::value, 192>(a, grid, st); });
+  return epi_dispatch(EpisStep{}, epi, STONK_ESHAPE, [&](auto e) { return launch_a4<decltype(e)::value, 256>(a, grid, st); });
 }

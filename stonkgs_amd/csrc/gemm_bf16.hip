@@ -43,18 +43,10 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(const GemmArgs p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
 
-  int M = p.M;
-  if (p.m_dev) {
-    const int md = *p.m_dev;
-    M = md < M ? md : M;
-  }
+  const int M = live_count(p.m_dev, p.M);
   const int ntm = (M + BM - 1) / BM, ntn = p.N / BN;
   // contraction length may also live in device memory (label-sparse wgrad): tiles past it are skipped
-  int nk_total = p.K / BK;
-  if (p.k_dev) {
-    const int kd = (*p.k_dev + BK - 1) / BK;
-    nk_total = kd < nk_total ? kd : nk_total;
-  }
+  const int nk_total = live_count(p.k_dev, p.K / BK, BK);
   const int nk_per = (nk_total + p.split_k - 1) / p.split_k;
   const int per_split = ntm * ntn;
   const int total = per_split * p.split_k;
@@ -71,15 +63,8 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(const GemmArgs p) {
     const int t = one_shot ? xcd_remap(t0, total) : t0;
     const int ks = t / per_split;
     const int tt = t - ks * per_split;
-    int rt, ct;
-    if (ntm >= ntn) {
-      rt = tt / ntn;
-      ct = tt - rt * ntn;
-    } else {
-      ct = tt / ntm;
-      rt = tt - ct * ntm;
-    }
-    const int m0 = rt * BM, n0 = ct * BN;
+    const TileRC rc = tile_split(tt, ntm, ntn);
+    const int m0 = rc.rt * BM, n0 = rc.ct * BN;
     const long k_begin = (long)ks * nk_per * BK;
     int nk = nk_total - ks * nk_per;
     nk = nk < nk_per ? nk : nk_per;
@@ -300,18 +285,8 @@ int launch_tile128(const GemmArgs& a, int out_mode, hipStream_t st) {
   if (out_mode == STONK_EPI_OUT_F32_ATOMIC) return launch<2, true, -1>(a, grid, st);
   if (out_mode == STONK_EPI_OUT_F16) return launch<3, true, 0>(a, grid, st);
   if (out_mode == STONK_EPI_OUT_F32) return epi == 0 ? launch<1, true, 0>(a, grid, st) : launch<1, true, -1>(a, grid, st);
-  switch (epi) {
-    case 0: return launch<0, true, 0>(a, grid, st);
-    case B: return launch<0, true, B>(a, grid, st);
-    case B | G | SV: return launch<0, true, B | G | SV>(a, grid, st);
-    case GB: return launch<0, true, GB>(a, grid, st);
-    case B | G | SV | AG: return launch<0, true, B | G | SV | AG>(a, grid, st);
-    case GB | AG: return launch<0, true, GB | AG>(a, grid, st);
-    case R: return launch<0, true, R>(a, grid, st);
-    case B | R: return launch<0, true, B | R>(a, grid, st);
-    case B | R | D: return launch<0, true, B | R | D>(a, grid, st);
-    default: return launch<0, true, -1>(a, grid, st);
-  }
+  if (!EpisTile128::has(epi)) return launch<0, true, -1>(a, grid, st);
+  return epi_dispatch(EpisTile128{}, epi, STONK_ESHAPE, [&](auto e) { return launch<0, true, decltype(e)::value>(a, grid, st); });
 }
 
 // what stonk_gemm_nt_bf16 decides: which of the four kernels, on which tile width (the four-wave kernels: 256, 192, or

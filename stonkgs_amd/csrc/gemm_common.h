@@ -2,6 +2,8 @@
 // weight-gradient forms gemm_tn.hip, gemm_tn_a4.hip): device-side epilogues, waits and tile mapping first, the launchers'
 // host-side helpers at the end. See stonk_gemm_nt_bf16 in include/stonk_hip.h for the meaning of each field.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 #include "stonk_flags.h"
 
@@ -51,79 +53,95 @@ struct Work {
   int nk;           // K tiles in this work item
 };
 
-// Fused epilogue on 4 consecutive output columns n..n+3 of row m (values already scaled by alpha).
-__device__ __forceinline__ f32x4 epilogue4(f32x4 v, const GemmArgs& p, int flags, int m, int n) {
-  if (flags & STONK_EPI_BIAS) v += *(const f32x4*)(p.bias + n);
+// A capacity that a count in device memory may lower: min(cap, ceil(*dev / per)). Rows (m_dev) and tokens (k_dev) with
+// per = 1, K tiles (k_dev) with per = 64. (all six kernels; gemm256.hip clamps its rows in its own text - with this helper
+// its register allocation came out differently)
+__device__ __forceinline__ int live_count(const int* dev, int cap, int per = 1) {
+  if (dev) {
+    const int d = (*dev + per - 1) / per;
+    cap = d < cap ? d : cap;
+  }
+  return cap;
+}
+
+// Tile tt of ntm x ntn -> (row tile, column tile), walking the SHORTER dimension fastest, so that consecutive tiles share
+// the operand panel of the longer one. (all six kernels)
+struct TileRC {
+  int rt, ct;
+};
+__device__ __forceinline__ TileRC tile_split(int tt, int ntm, int ntn) {
+  if (ntm >= ntn) {
+    const int rt = tt / ntn;
+    return {rt, tt - rt * ntn};
+  }
+  const int ct = tt / ntm;
+  return {tt - ct * ntm, ct};
+}
+
+// The next work item of this workgroup that has K tiles (k_dev may leave a K split empty): wi += G until get_work(wi, out)
+// says there is none (false) or out.nk > 0. (gemm_tn_a4.hip, gemm_w4.hip's prefetch cursor; the other skip-empty loops of
+// gemm256.hip and gemm_w4.hip compile to other instructions through it and keep their own text)
+template <typename GetWork, typename W>
+__device__ __forceinline__ bool next_live_work(GetWork&& get_work, int& wi, int G, W& out) {
+  do {
+    wi += G;
+    if (!get_work(wi, out)) return false;
+  } while (out.nk <= 0);
+  return true;
+}
+
+// The element-wise stages of the fused epilogue on W consecutive output columns n..n+W-1 of row m (values already scaled
+// by alpha), in their one order: bias, saved pre-activation (or GELU'; stored from here), GELU, GELU', dropout, residual.
+// v: f32x4 or float[W]. Side operands: bias() = the W fp32 of the bias, aux() / res() = the W bf16 of the GELU' input /
+// the residual, each asked for at its stage (a caller without prefetched ones loads them there). epilogue4 and
+// epilogue8_pre are this chain; gemm_bf16.hip's constant-flag epilogue keeps the same stages in its own text (through the
+// chain it needs two more VGPRs), and gemm_w4.hip / gemm_a4.hip do bias and GELU themselves and pass the rest here.
+template <int W, typename V, typename Bias, typename Aux, typename Res>
+__device__ __forceinline__ void epilogue_chain(V& v, const GemmArgs& p, int flags, int m, int n, Bias&& bias, Aux&& aux, Res&& res) {
+  typedef bf16 bf16xW __attribute__((ext_vector_type(W)));
+  if (flags & STONK_EPI_BIAS) {
+    const auto b = bias();
+#pragma unroll
+    for (int r = 0; r < W; ++r) v[r] += b[r];
+  }
   if (flags & STONK_EPI_SAVE_PREACT) {
-    const bool ag = (flags & STONK_EPI_AUX_GRAD) != 0;
-    bf16x4 u = {(bf16)gelu_saved(v[0], ag), (bf16)gelu_saved(v[1], ag), (bf16)gelu_saved(v[2], ag),
-                (bf16)gelu_saved(v[3], ag)};
-    *(bf16x4*)(p.aux + (long)m * p.ldaux + n) = u;
+    bf16xW u;
+#pragma unroll
+    for (int r = 0; r < W; ++r) u[r] = (bf16)gelu_saved(v[r], (flags & STONK_EPI_AUX_GRAD) != 0);
+    *(bf16xW*)(p.aux + (long)m * p.ldaux + n) = u;
   }
   if (flags & STONK_EPI_GELU) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) v[r] = gelu_erf(v[r]);
+    for (int r = 0; r < W; ++r) v[r] = gelu_erf(v[r]);
   }
   if (flags & STONK_EPI_GELU_BWD) {
-    const bf16x4 u = *(const bf16x4*)(p.aux + (long)m * p.ldaux + n);
+    const bf16xW u = aux();
 #pragma unroll
-    for (int r = 0; r < 4; ++r) v[r] *= gelu_factor((float)u[r], (flags & STONK_EPI_AUX_GRAD) != 0);
+    for (int r = 0; r < W; ++r) v[r] *= gelu_factor((float)u[r], (flags & STONK_EPI_AUX_GRAD) != 0);
   }
   if (flags & STONK_EPI_DROPOUT) {
     const uint32_t rk = stonk_rowkey((uint32_t)m, p.seed), ck = stonk_colkey((uint32_t)n);
 #pragma unroll
-    for (int r = 0; r < 4; ++r)
+    for (int r = 0; r < W; ++r)
       v[r] = stonk_keep_key(rk, ck + (uint32_t)r * STONK_G_COL, p.drop_thr32) ? v[r] * p.drop_scale : 0.f;
   }
   if (flags & STONK_EPI_RESID) {
-    const bf16x4 rr = *(const bf16x4*)(p.resid + (long)m * p.ldr + n);
+    const bf16xW rr = res();
 #pragma unroll
-    for (int r = 0; r < 4; ++r) v[r] += (float)rr[r];
+    for (int r = 0; r < W; ++r) v[r] += (float)rr[r];
   }
+}
+
+// Fused epilogue on 4 consecutive output columns n..n+3 of row m (values already scaled by alpha), side operands loaded here.
+__device__ __forceinline__ f32x4 epilogue4(f32x4 v, const GemmArgs& p, int flags, int m, int n) {
+  epilogue_chain<4>(v, p, flags, m, n, [&] { return *(const f32x4*)(p.bias + n); },
+                    [&] { return *(const bf16x4*)(p.aux + (long)m * p.ldaux + n); },
+                    [&] { return *(const bf16x4*)(p.resid + (long)m * p.ldr + n); });
   return v;
 }
 
-// Fused epilogue on 8 consecutive output columns n..n+7 of row m (fp32 values already scaled by alpha): every side
-// operand (bias, saved pre-activation, residual) is read / written as one 16- or 32-byte vector.
-__device__ __forceinline__ void epilogue8(float (&v)[8], const GemmArgs& p, int flags, int m, int n) {
-  if (flags & STONK_EPI_BIAS) {
-    const f32x4 b0 = *(const f32x4*)(p.bias + n), b1 = *(const f32x4*)(p.bias + n + 4);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      v[r] += b0[r];
-      v[4 + r] += b1[r];
-    }
-  }
-  if (flags & STONK_EPI_SAVE_PREACT) {
-    bf16x8 u;
-#pragma unroll
-    for (int r = 0; r < 8; ++r) u[r] = (bf16)gelu_saved(v[r], (flags & STONK_EPI_AUX_GRAD) != 0);
-    *(bf16x8*)(p.aux + (long)m * p.ldaux + n) = u;
-  }
-  if (flags & STONK_EPI_GELU) {
-#pragma unroll
-    for (int r = 0; r < 8; ++r) v[r] = gelu_erf(v[r]);
-  }
-  if (flags & STONK_EPI_GELU_BWD) {
-    const bf16x8 u = *(const bf16x8*)(p.aux + (long)m * p.ldaux + n);
-#pragma unroll
-    for (int r = 0; r < 8; ++r) v[r] *= gelu_factor((float)u[r], (flags & STONK_EPI_AUX_GRAD) != 0);
-  }
-  if (flags & STONK_EPI_DROPOUT) {
-    const uint32_t rk = stonk_rowkey((uint32_t)m, p.seed), ck = stonk_colkey((uint32_t)n);
-#pragma unroll
-    for (int r = 0; r < 8; ++r)
-      v[r] = stonk_keep_key(rk, ck + (uint32_t)r * STONK_G_COL, p.drop_thr32) ? v[r] * p.drop_scale : 0.f;
-  }
-  if (flags & STONK_EPI_RESID) {
-    const bf16x8 rr = *(const bf16x8*)(p.resid + (long)m * p.ldr + n);
-#pragma unroll
-    for (int r = 0; r < 8; ++r) v[r] += (float)rr[r];
-  }
-}
-
-// Side operands of one epilogue8 call, fetched AHEAD of their use (one round earlier) so that the global-load latency
-// of the residual / saved pre-activation is not paid once per 16-row round.
+// Side operands (8 consecutive columns of one row) of one epilogue8_pre call, fetched AHEAD of their use (one round
+// earlier) so that the global-load latency of the residual / saved pre-activation is not paid once per 16-row round.
 struct SideOps {
   bf16x8 aux, res;
 };
@@ -141,49 +159,44 @@ __device__ __forceinline__ bf16x8 side_load1(const GemmArgs& p, int flags, int m
   if (flags & STONK_EPI_GELU_BWD) return *(const bf16x8*)(p.aux + (long)m * p.ldaux + n);
   return *(const bf16x8*)(p.resid + (long)m * p.ldr + n);
 }
-// epilogue8 with preloaded bias (8 columns of this lane, fixed for the whole tile) and side operands
+// Fused epilogue on 8 consecutive output columns n..n+7 of row m (fp32 values already scaled by alpha), with preloaded
+// bias (8 columns of this lane, fixed for the whole tile) and side operands
 __device__ __forceinline__ void epilogue8_pre(float (&v)[8], const GemmArgs& p, int flags, int m, int n, const f32x4& b0,
                                               const f32x4& b1, const SideOps& s) {
-  if (flags & STONK_EPI_BIAS) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      v[r] += b0[r];
-      v[4 + r] += b1[r];
-    }
-  }
-  if (flags & STONK_EPI_SAVE_PREACT) {
-    bf16x8 u;
-#pragma unroll
-    for (int r = 0; r < 8; ++r) u[r] = (bf16)gelu_saved(v[r], (flags & STONK_EPI_AUX_GRAD) != 0);
-    *(bf16x8*)(p.aux + (long)m * p.ldaux + n) = u;
-  }
-  if (flags & STONK_EPI_GELU) {
-#pragma unroll
-    for (int r = 0; r < 8; ++r) v[r] = gelu_erf(v[r]);
-  }
-  if (flags & STONK_EPI_GELU_BWD) {
-#pragma unroll
-    for (int r = 0; r < 8; ++r) v[r] *= gelu_factor((float)s.aux[r], (flags & STONK_EPI_AUX_GRAD) != 0);
-  }
-  if (flags & STONK_EPI_DROPOUT) {
-    const uint32_t rk = stonk_rowkey((uint32_t)m, p.seed), ck = stonk_colkey((uint32_t)n);
-#pragma unroll
-    for (int r = 0; r < 8; ++r)
-      v[r] = stonk_keep_key(rk, ck + (uint32_t)r * STONK_G_COL, p.drop_thr32) ? v[r] * p.drop_scale : 0.f;
-  }
-  if (flags & STONK_EPI_RESID) {
-#pragma unroll
-    for (int r = 0; r < 8; ++r) v[r] += (float)s.res[r];
-  }
+  epilogue_chain<8>(v, p, flags, m, n, [&] { return __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7); },
+                    [&] { return s.aux; }, [&] { return s.res; });
 }
 
 // ---------------------------------------------------------------- host side: what every launcher does
-// Epilogue bits by their short names, for the launchers' switch (epi) blocks that name the compiled instances.
+// The epilogues (flags & epi_bits::MASK) that are compiled with constant flags are listed as types: a launcher asks its
+// kernel's list whether there is an instance (has) and launches it through the same list (epi_dispatch), so the two cannot
+// disagree.
+template <int... E>
+struct EpiList {
+  static constexpr bool has(int epi) { return ((epi == E) || ...); }
+};
+// Epilogue bits by their short names, and the lists of compiled instances in them.
 namespace epi_bits {
 constexpr int B = STONK_EPI_BIAS, G = STONK_EPI_GELU, SV = STONK_EPI_SAVE_PREACT, GB = STONK_EPI_GELU_BWD,
               R = STONK_EPI_RESID, D = STONK_EPI_DROPOUT, AG = STONK_EPI_AUX_GRAD;
 constexpr int MASK = B | G | SV | GB | R | D | AG;   // = 0x1FC: flags & MASK == 0 is the plain product
+// the eight of the training step that every bf16 NT kernel has an instance of, and what a kernel has besides them
+template <int... MORE>
+using EpisCommon = EpiList<0, B, B | G | SV, GB, B | G | SV | AG, GB | AG, R, B | R, MORE...>;
+using EpisStep = EpisCommon<B | G, B | R | D>;   // the step's ten: gemm_w4.hip, gemm_a4.hip
+using EpisTile128 = EpisCommon<B | R | D>;       // gemm_bf16.hip
+using EpisWave8 = EpisCommon<B | G>;             // gemm256.hip (bias + dropout + residual would spill there)
+// the four-wave kernels' 256 x 192 tiles exist for the epilogues of the N = 768 launches
+using Epis192 = EpiList<0, B, R, B | R, B | R | D>;
 }  // namespace epi_bits
+
+// f(std::integral_constant<int, epi>) for the member of the list that equals the run-time `epi`; `fallback` if there is none
+template <int... E, typename F>
+int epi_dispatch(EpiList<E...>, int epi, int fallback, F&& f) {
+  int rc = fallback;
+  (void)((epi == E && ((rc = f(std::integral_constant<int, E>{})), true)) || ...);
+  return rc;
+}
 
 // CUs of the current device, asked once per process (one process per GPU); <= 0: the query failed, hipGetLastError() says why
 inline int cu_count() {
@@ -210,13 +223,8 @@ int launch_with_lds(const Args& a, int grid, int block, hipStream_t st) {
   return stonk_launch_status();
 }
 
-// The four-wave kernels' 256 x (256 | 192) tiles (gemm_w4.hip, gemm_a4.hip). 192-wide instances exist for the epilogues of
-// the N = 768 launches (none, bias, residual, bias + residual [+ dropout]) ...
-inline bool epi_has_192(int e) {
-  using namespace epi_bits;
-  return e == 0 || e == B || e == R || e == (B | R) || e == (B | R | D);
-}
-// ... and are chosen (tile_n == 0 on entry) where they quantise better: time ~ rounds of the CUs x tile width (N = 768 at
+// The four-wave kernels' 256 x (256 | 192) tiles (gemm_w4.hip, gemm_a4.hip): where there is a 192-wide instance (has192:
+// Epis192, N % 192 == 0) it is chosen (tile_n == 0 on entry) where it quantises better: time ~ rounds of the CUs x tile width (N = 768 at
 // 32 768 rows: two full rounds instead of one and a half; at 16 384 rows one full round instead of 3/4). Returns the grid:
 // one persistent workgroup per CU, or (items_per_wg > 0) work items / items_per_wg. k_shares: work items per output tile.
 inline int tile_grid_256(const GemmArgs& a, bool has192, long k_shares, int items_per_wg, int n_cu, int& tile_n) {

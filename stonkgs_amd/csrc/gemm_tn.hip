@@ -32,6 +32,8 @@ constexpr int TILE_BYTES = BK * 256;          // 16 KiB: 64 token rows x 128 fea
 constexpr int STAGE_BYTES = 2 * TILE_BYTES;
 constexpr int TN_LDS = 2 * STAGE_BYTES;       // 64 KiB
 
+using stonk_gemm::live_count;
+using stonk_gemm::tile_split;
 using stonk_gemm::xcd_remap;
 
 struct TnArgs {
@@ -66,11 +68,7 @@ __device__ __forceinline__ void gemm_tn_body(const TnArgs& p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
 
-  int K = p.K;
-  if (p.k_dev) {
-    const int kd = *p.k_dev;
-    K = kd < K ? kd : K;
-  }
+  const int K = live_count(p.k_dev, p.K);
   const int nk_total = (K + BK - 1) / BK;   // rows in [K, roundup) must read as zero (caller guarantees)
   const int ntm = p.M / BM, ntn = p.N / BN;
   const int nk_per = (nk_total + p.split_k - 1) / p.split_k;
@@ -79,14 +77,8 @@ __device__ __forceinline__ void gemm_tn_body(const TnArgs& p) {
   const int t = ((int)gridDim.x == total) ? xcd_remap(blockIdx.x, total) : blockIdx.x;
   const int ks = t / per_split;
   const int tt = t - ks * per_split;
-  int rt, ct;
-  if (ntm >= ntn) {
-    rt = tt / ntn;
-    ct = tt - rt * ntn;
-  } else {
-    ct = tt / ntm;
-    rt = tt - ct * ntm;
-  }
+  const stonk_gemm::TileRC rc = tile_split(tt, ntm, ntn);
+  const int rt = rc.rt, ct = rc.ct;
   const int m0 = rt * BM, n0 = ct * BN;
   int nk = nk_total - ks * nk_per;
   nk = nk < nk_per ? nk : nk_per;

@@ -76,11 +76,7 @@ __global__ __launch_bounds__(256, 1) void STONK_TN_A4_KERNEL(const GemmArgs p) {
   const int wr = wave >> 1, wc = wave & 1;
 
   const int M = p.M, N = p.N;
-  int Kact = p.K;
-  if (p.k_dev) {
-    const int kd = *p.k_dev;
-    Kact = kd < Kact ? kd : Kact;
-  }
+  const int Kact = live_count(p.k_dev, p.K);
   const int ntm = (M + BM - 1) / BM, ntn = (N + BN - 1) / BN;
   const int nk_total = (Kact + BK - 1) / BK;
   int nk_per = (nk_total + p.split_k - 1) / p.split_k;
@@ -118,27 +114,13 @@ __global__ __launch_bounds__(256, 1) void STONK_TN_A4_KERNEL(const GemmArgs p) {
     }
     const int ks = idx / per_split;
     const int tt = idx - ks * per_split;
-    int rt, ct;
-    if (ntm >= ntn) {
-      rt = tt / ntn;
-      ct = tt - rt * ntn;
-    } else {
-      ct = tt / ntm;
-      rt = tt - ct * ntm;
-    }
-    o.m0 = rt * BM;
-    o.n0 = ct * BN;
+    const TileRC t = tile_split(tt, ntm, ntn);
+    o.m0 = t.rt * BM;
+    o.n0 = t.ct * BN;
     o.k_begin = (long)ks * nk_per * BK;
     int nk = nk_total - ks * nk_per;
     nk = nk < nk_per ? nk : nk_per;
     o.nk = nk <= 0 ? 0 : nk + (nk & 1);   // (even; tokens past the end read as zeros)
-    return true;
-  };
-  auto next_work = [&](int& wi, Work& o) -> bool {   // (k_dev may leave a K split empty)
-    do {
-      wi += G;
-      if (!get_work(wi, o)) return false;
-    } while (o.nk <= 0);
     return true;
   };
 
@@ -189,17 +171,13 @@ __global__ __launch_bounds__(256, 1) void STONK_TN_A4_KERNEL(const GemmArgs p) {
   Work cw, nw;
   int cwi = blockIdx.x;
   if (!get_work(cwi, cw)) return;
-  if (cw.nk <= 0 && !next_work(cwi, cw)) return;
+  if (cw.nk <= 0 && !next_live_work(get_work, cwi, G, cw)) return;   // (k_dev may leave a K split empty)
   Cursor ca, cb;
   cursor_of(cw, ca, cb);
   const int stepa = BK * lda2, stepb = BK * ldb2;
 
-#define STONK_TN_A4_DMA_OPERANDS                                                                                        \
-  [voffA0] "v"(voffA[0]), [voffA1] "v"(voffA[1]), [voffA2] "v"(voffA[2]), [voffA3] "v"(voffA[3]), [voffA4] "v"(voffA[4]), \
-      [voffA5] "v"(voffA[5]), [voffA6] "v"(voffA[6]), [voffA7] "v"(voffA[7]), [voffB0] "v"(voffB[0]),                   \
-      [voffB1] "v"(voffB[1]), [voffB2] "v"(voffB[2]), [voffB3] "v"(voffB[3]), [voffB4] "v"(voffB[4]),                   \
-      [voffB5] "v"(voffB[5]), [voffB6] "v"(voffB[6]), [voffB7] "v"(voffB[7]), [m0a] "s"(m0a), [m0b] "s"(m0b),           \
-      [stepa] "s"(stepa), [stepb] "s"(stepb)
+#define STONK_TN_A4_DMA_OPERANDS \
+  STONK_A4_VOFF_IN(voffA, voffB), [m0a] "s"(m0a), [m0b] "s"(m0b), [stepa] "s"(stepa), [stepb] "s"(stepb)
 
   // K tiles 0 and 1 of the first work item
   asm volatile(STONK_TN_A4_PROLOGUE
@@ -213,7 +191,7 @@ __global__ __launch_bounds__(256, 1) void STONK_TN_A4_KERNEL(const GemmArgs p) {
 
   for (;;) {
     int nwi = cwi;
-    const bool more = next_work(nwi, nw);
+    const bool more = next_live_work(get_work, nwi, G, nw);
     Cursor na, nb;
     cursor_of(more ? nw : cw, na, nb);   // (no next item: the cursor re-reads this item's first K tiles, never consumed)
     f32x16 acc[16];
@@ -226,22 +204,8 @@ __global__ __launch_bounds__(256, 1) void STONK_TN_A4_KERNEL(const GemmArgs p) {
     const int kt0 = (int)(cw.k_begin / BK);
     int bph = want_bias ? ((kt0 - ct) % ntn + ntn) % ntn : 1;
     const int ntn_s = want_bias ? ntn : 0x7fffffff;   // (without a bias the phase never returns to 0)
-#define STONK_A4_CLOBBERS_TN                                                                                           \
-  "m0", "scc", "s48", "memory", "v128", "v129", "v130", "v131", "v132", "v133", "v134", "v135", "v136", "v137", "v138", \
-      "v139", "v140", "v141", "v142", "v143", "v144", "v145", "v146", "v147", "v148", "v149", "v150", "v151", "v152",  \
-      "v153", "v154", "v155", "v156", "v157", "v158", "v159", "v160", "v161", "v162", "v163", "v164", "v165", "v166",  \
-      "v167", "v168", "v169", "v170", "v171", "v172", "v173", "v174", "v175", "v176", "v177", "v178", "v179", "v180",  \
-      "v181", "v182", "v183", "v184", "v185", "v186", "v187", "v188", "v189", "v190", "v191", "v192", "v193", "v194",  \
-      "v195", "v196", "v197", "v198", "v199", "v200", "v201", "v202", "v203", "v204", "v205", "v206", "v207", "v208",  \
-      "v209", "v210", "v211", "v212", "v213", "v214", "v215", "v216", "v217", "v218", "v219", "v220", "v221", "v222",  \
-      "v223", "v224", "v225", "v226", "v227", "v228", "v229", "v230", "v231", "v232", "v233", "v234", "v235", "v236",  \
-      "v237", "v238", "v239", "v240", "v241", "v242", "v243", "v244", "v245", "v246", "v247", "v248", "v249", "v250",  \
-      "v251", "v252", "v253", "v254", "v255"
     asm volatile(STONK_TN_A4_TILE
-                 : "={a[0:15]}"(acc[0]), "={a[16:31]}"(acc[1]), "={a[32:47]}"(acc[2]), "={a[48:63]}"(acc[3]),
-                   "={a[64:79]}"(acc[4]), "={a[80:95]}"(acc[5]), "={a[96:111]}"(acc[6]), "={a[112:127]}"(acc[7]),
-                   "={a[128:143]}"(acc[8]), "={a[144:159]}"(acc[9]), "={a[160:175]}"(acc[10]), "={a[176:191]}"(acc[11]),
-                   "={a[192:207]}"(acc[12]), "={a[208:223]}"(acc[13]), "={a[224:239]}"(acc[14]), "={a[240:255]}"(acc[15]),
+                 : STONK_A4_ACC_OUT_16(acc),
                    "+{s[36:39]}"(ca.srd), "+{s[40:43]}"(cb.srd), [ralo] "+s"(ca.rem_lo), [rahi] "+s"(ca.rem_hi),
                    [rblo] "+s"(cb.rem_lo), [rbhi] "+s"(cb.rem_hi), [rem] "+s"(rem), [bph] "+s"(bph),
                    [bacc0] "+v"(bacc[0]), [bacc1] "+v"(bacc[1]), [bacc2] "+v"(bacc[2]), [bacc3] "+v"(bacc[3]),
@@ -252,7 +216,7 @@ __global__ __launch_bounds__(256, 1) void STONK_TN_A4_KERNEL(const GemmArgs p) {
                    [taB6] "v"(taB[6]), [taB7] "v"(taB[7]), [ones] "v"(ones), [ntn] "s"(ntn_s),
                    [nal] "s"(na.srd[0]), [nah] "s"(na.srd[1]), [nralo] "s"(na.rem_lo), [nrahi] "s"(na.rem_hi),
                    [nbl] "s"(nb.srd[0]), [nbh] "s"(nb.srd[1]), [nrblo] "s"(nb.rem_lo), [nrbhi] "s"(nb.rem_hi)
-                 : STONK_A4_CLOBBERS_TN);
+                 : "m0", "scc", "s48", "memory", STONK_A4_FRAG_CLOBBERS);
 
     // ---- epilogue: accumulator block (i, j) = a[4 (8 i + j) ..]: lane (n = lane & 15, qq) holds rows 16 i + 4 qq + e, column
     // 16 j + n. A v_permlane16_swap of the blocks (i, 2 jp) = x and (i, 2 jp + 1) = y leaves, per register e,
@@ -286,18 +250,7 @@ __global__ __launch_bounds__(256, 1) void STONK_TN_A4_KERNEL(const GemmArgs p) {
           ys[jp][e] = acc[by >> 2][4 * (by & 3) + e];
         }
       }
-#define STONK_A4_SWAP4(a, b) "v_permlane16_swap_b32 %" #a ", %" #b "\n"
-      asm volatile("s_nop 1\n" STONK_A4_SWAP4(0, 16) STONK_A4_SWAP4(1, 17) STONK_A4_SWAP4(2, 18) STONK_A4_SWAP4(3, 19)
-                   STONK_A4_SWAP4(4, 20) STONK_A4_SWAP4(5, 21) STONK_A4_SWAP4(6, 22) STONK_A4_SWAP4(7, 23)
-                   STONK_A4_SWAP4(8, 24) STONK_A4_SWAP4(9, 25) STONK_A4_SWAP4(10, 26) STONK_A4_SWAP4(11, 27)
-                   STONK_A4_SWAP4(12, 28) STONK_A4_SWAP4(13, 29) STONK_A4_SWAP4(14, 30) STONK_A4_SWAP4(15, 31) "s_nop 1"
-                   : "+v"(xs[0][0]), "+v"(xs[0][1]), "+v"(xs[0][2]), "+v"(xs[0][3]), "+v"(xs[1][0]), "+v"(xs[1][1]),
-                     "+v"(xs[1][2]), "+v"(xs[1][3]), "+v"(xs[2][0]), "+v"(xs[2][1]), "+v"(xs[2][2]), "+v"(xs[2][3]),
-                     "+v"(xs[3][0]), "+v"(xs[3][1]), "+v"(xs[3][2]), "+v"(xs[3][3]),
-                     "+v"(ys[0][0]), "+v"(ys[0][1]), "+v"(ys[0][2]), "+v"(ys[0][3]), "+v"(ys[1][0]), "+v"(ys[1][1]),
-                     "+v"(ys[1][2]), "+v"(ys[1][3]), "+v"(ys[2][0]), "+v"(ys[2][1]), "+v"(ys[2][2]), "+v"(ys[2][3]),
-                     "+v"(ys[3][0]), "+v"(ys[3][1]), "+v"(ys[3][2]), "+v"(ys[3][3]));
-#undef STONK_A4_SWAP4
+      asm volatile(STONK_A4_SWAP_4(xs, ys));
       const int mrow = wm0 + 16 * i + 8 * (lane >> 5);
 #if STONK_TN_A4_STORE == 2
       float sq[4][4];   // (added up as a tree per row block, the eight row blocks one after the other: a short chain)
@@ -363,7 +316,6 @@ __global__ __launch_bounds__(256, 1) void STONK_TN_A4_KERNEL(const GemmArgs p) {
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #undef STONK_TN_A4_DMA_OPERANDS
-#undef STONK_A4_CLOBBERS_TN
 }
 
 }  // namespace

@@ -62,18 +62,10 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const GemmArgs p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 1, wc = wave & 1;
 
-  int M = p.M;
-  if (p.m_dev) {
-    const int md = *p.m_dev;
-    M = md < M ? md : M;
-  }
+  const int M = live_count(p.m_dev, p.M);
   const int N = p.N;
   const int ntm = (M + BM - 1) / BM, ntn = (N + BN - 1) / BN;
-  int nk_total = p.K / BK;
-  if (p.k_dev) {
-    const int kd = (*p.k_dev + BK - 1) / BK;
-    nk_total = kd < nk_total ? kd : nk_total;
-  }
+  const int nk_total = live_count(p.k_dev, p.K / BK, BK);
   const int nk_per = (nk_total + p.split_k - 1) / p.split_k;
   const int per_split = ntm * ntn;
   const int total = per_split * p.split_k;
@@ -97,16 +89,9 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const GemmArgs p) {
     }
     const int ks = idx / per_split;
     const int tt = idx - ks * per_split;
-    int rt, ct;
-    if (ntm >= ntn) {
-      rt = tt / ntn;
-      ct = tt - rt * ntn;
-    } else {
-      ct = tt / ntm;
-      rt = tt - ct * ntm;
-    }
-    o.m0 = rt * BM;
-    o.n0 = ct * BN;
+    const TileRC t = tile_split(tt, ntm, ntn);
+    o.m0 = t.rt * BM;
+    o.n0 = t.ct * BN;
     o.k_begin = (long)ks * nk_per * BK;
     int nk = nk_total - ks * nk_per;
     o.nk = nk < nk_per ? nk : nk_per;
@@ -207,12 +192,7 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const GemmArgs p) {
     }
     Work nw;
     int nwi = pwi;
-    bool ok;
-    do {
-      nwi += G;
-      ok = get_work(nwi, nw);
-    } while (ok && nw.nk <= 0);
-    if (!ok) {
+    if (!next_live_work(get_work, nwi, G, nw)) {
       p_valid = false;
       return;
     }
@@ -520,31 +500,14 @@ int stonk_gemm_w4_launch(const GemmArgs& a, int out_mode, int tile_n, int items_
   const int n_cu = cu_count();
   if (n_cu <= 0) return (int)hipGetLastError();
   const int epi = a.flags & MASK;
-  const bool has192 = out_mode == 0 && a.N % 192 == 0 && epi_has_192(epi);
+  const bool has192 = out_mode == 0 && a.N % 192 == 0 && Epis192::has(epi);
   if (tile_n == 192 && !has192) return STONK_ESHAPE;
   const int grid = tile_grid_256(a, has192, a.split_k, items_per_wg, n_cu, tile_n);
-  if (tile_n == 192) {
-    switch (epi) {
-      case 0: return launch_w4<0, 0, 192>(a, grid, st);
-      case B: return launch_w4<0, B, 192>(a, grid, st);
-      case R: return launch_w4<0, R, 192>(a, grid, st);
-      case B | R: return launch_w4<0, B | R, 192>(a, grid, st);
-      default: return launch_w4<0, B | R | D, 192>(a, grid, st);
-    }
-  }
+  if (tile_n == 192)
+    return epi_dispatch(Epis192{}, epi, STONK_ESHAPE, [&](auto e) { return launch_w4<0, decltype(e)::value, 192>(a, grid, st); });
   if (out_mode == 1) return epi == 0 ? launch_w4<1, 0>(a, grid, st) : launch_w4<1, -1>(a, grid, st);
   if (out_mode == 2) return launch_w4<2, 0>(a, grid, st);
-  switch (epi) {   // the combinations the STonKGs step uses are compiled with constant flags
-    case 0: return launch_w4<0, 0>(a, grid, st);
-    case B: return launch_w4<0, B>(a, grid, st);
-    case B | G: return launch_w4<0, B | G>(a, grid, st);
-    case B | G | SV: return launch_w4<0, B | G | SV>(a, grid, st);
-    case GB: return launch_w4<0, GB>(a, grid, st);
-    case B | G | SV | AG: return launch_w4<0, B | G | SV | AG>(a, grid, st);
-    case GB | AG: return launch_w4<0, GB | AG>(a, grid, st);
-    case R: return launch_w4<0, R>(a, grid, st);
-    case B | R: return launch_w4<0, B | R>(a, grid, st);
-    case B | R | D: return launch_w4<0, B | R | D>(a, grid, st);
-    default: return launch_w4<0, -1>(a, grid, st);
-  }
+  // the combinations the STonKGs step uses are compiled with constant flags
+  if (!EpisStep::has(epi)) return launch_w4<0, -1>(a, grid, st);
+  return epi_dispatch(EpisStep{}, epi, STONK_ESHAPE, [&](auto e) { return launch_w4<0, decltype(e)::value>(a, grid, st); });
 }

@@ -26,7 +26,7 @@ RANDOM data (and the transcendental epilogues on exact data): `check_bound`, for
            cases run on exact data (their S is taken as 0: the product carries no error), so a_extra is their whole
            tolerance.
 
-Order of the epilogue (gemm_common.h epilogue8): alpha, bias, saved value (pre-activation or gelu'), GELU, * gelu'(aux) (or
+Order of the epilogue (gemm_common.h epilogue8_pre): alpha, bias, saved value (pre-activation or gelu'), GELU, * gelu'(aux) (or
 * aux with AUX_GRAD), dropout scaled by float32(1 / (1 - float32(p))), residual. The atomic output adds alpha * product
 into what C held and takes no epilogue.
 """

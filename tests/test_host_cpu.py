@@ -458,3 +458,15 @@ def test_written_out_kernels_use_no_scratch():
     attn = kr.kernel_resources(os.path.join(csrc, "attention.o"))
     bad = [(k["name"], k["scratch"]) for k in attn if k["scratch"] or k.get("vgpr_spill", 0)]
     assert len(attn) == 13 and not bad, bad
+
+
+def test_generated_gemm_loop_is_up_to_date():
+    """stonkgs_amd/csrc/gemm_a4_loop.inc is generated text that is committed: it must be what tools/gen_gemm_a4.py writes
+    today, or the written-out GEMM kernels are built from a schedule other than the one the generator describes."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("gen_gemm_a4", os.path.join(ROOT, "tools", "gen_gemm_a4.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    with open(os.path.join(ROOT, "stonkgs_amd", "csrc", "gemm_a4_loop.inc")) as f:
+        assert f.read() == gen.generate(None)

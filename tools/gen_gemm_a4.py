@@ -86,10 +86,13 @@ ADVANCE = ["s_add_u32 s36, s36, 128", "s_addc_u32 s37, s37, 0", "s_sub_u32 s38, 
            "s_add_u32 s40, s40, 128", "s_addc_u32 s41, s41, 0", "s_sub_u32 s42, s42, 128"]
 
 
-def ktile(c, stage, first, sched):
-    """One K tile: 2 * nm MFMAs with the side instructions placed in the gaps after them (gap g = after MFMA g). A gap
-    carries at most ONE memory instruction (an LDS read or an LDS-DMA issue): `place` takes the first free gap at or
-    after the one asked for. `ablate` (timing experiments only, results are garbage): "dma" / "reads" leave those out."""
+def ktile(c, stage, first, sched, reads, advance, mfma_of, row_extra=None):
+    """One K tile of either form: 2 * nm MFMAs with the side instructions placed in the gaps after them (gap g = after
+    MFMA g). A gap carries at most ONE memory instruction (an LDS read - or the pair of transposed reads that make one
+    fragment - or an LDS-DMA issue): `place` takes the first free gap at or after the one asked for. What the two forms
+    differ in comes as arguments: reads(h, stage) = the fragment reads of k-half h, advance = the cursor bookkeeping, one
+    list per gap behind the last LDS-DMA issue, mfma_of(h, i, j, first) = the MFMA text, row_extra(h, i) = an instruction
+    behind row block i's MFMAs. `ablate` (timing experiments only, results are garbage): "dma" / "reads" leave those out."""
     nm = c.nm
     ablate = sched.get("ablate", ())
     side = [[] for _ in range(2 * nm)]
@@ -99,39 +102,36 @@ def ktile(c, stage, first, sched):
         while busy[g]:
             g += 1
         busy[g] = True
-        side[g].append(ins)
+        side[g] += ins if isinstance(ins, list) else [ins]
         return g
 
     # phase 1: k-half 1 of this K tile -> set 1
     g = sched["read1_start"]
     last_read = g
-    for ins in frag_reads(c, 1, stage):
+    for ins in reads(1, stage):
         if "reads" not in ablate:
             last_read = place(g, ins)
         g += sched["read_step"]
     b1 = sched["b1_gap"]
     assert last_read < b1, "reads must be issued before B1"
-    side[b1].append("s_waitcnt lgkmcnt(0)")
-    side[b1].append("s_barrier")
+    side[b1] += ["s_waitcnt lgkmcnt(0)", "s_barrier"]
     # B2: K tile t+1 (issued one K tile earlier) has landed; behind it, k-half 0 of K tile t+1 from the other stage -> set 0
     # (placed first: its gaps are fixed, the LDS-DMA issues then take the free gaps around them)
     b2 = nm + sched["b2_gap"]
     g = b2 + 1
-    step2 = sched.get("read2_step", sched["read_step"])
-    for ins in frag_reads(c, 0, stage ^ 1):
+    for ins in reads(0, stage ^ 1):
         if "reads" not in ablate:
             last_read = place(g, ins)
-        g += step2
+        g += sched.get("read2_step", sched["read_step"])
     assert last_read <= 2 * nm - 2, (last_read, 2 * nm)
     side[2 * nm - 2].append("s_waitcnt lgkmcnt(0)")
     # LDS-DMA of K tile t+2 into this stage, from B1 on: piece n in a gap of its own, the next piece's M0 one gap later (an
     # MFMA between a piece's issue and the M0 write behind it, and at least one between that write and its use)
     g = b1 + 2
-    ops = dma_ops(c, stage)
     assert sched["dma_step"] >= 2
     m0_gap = b1 + 1
     last_dma = b1
-    for n, (m0, ld) in enumerate(ops):
+    for m0, ld in dma_ops(c, stage):
         if "dma" in ablate:
             break
         side[m0_gap].append(m0)
@@ -139,9 +139,9 @@ def ktile(c, stage, first, sched):
         m0_gap = at + 1
         last_dma = at
         g = at + sched["dma_step"]
-    assert last_dma + 2 < 2 * nm, last_dma
-    side[last_dma + 1] += ADVANCE[0:3]       # (s_add / s_addc adjacent: nothing between them writes SCC)
-    side[last_dma + 2] += ADVANCE[3:6]
+    assert last_dma + len(advance) < 2 * nm, last_dma
+    for n, adv in enumerate(advance):        # (s_add / s_addc adjacent: nothing between them writes SCC)
+        side[last_dma + 1 + n] += adv
     # the wait of B2 counts what THIS K tile has issued before it: all but those pieces must be done
     issued = sum(1 for gg in range(b2) for ins in side[gg] if ins.startswith("buffer_load"))   # (gap b2 itself: wait first)
     if "dma" not in ablate:
@@ -152,9 +152,11 @@ def ktile(c, stage, first, sched):
     for h in range(2):
         for i in range(8):
             for j in range(c.nbj):
-                out.append(mfma(c, h, i, j, first and h == 0))
+                out.append(mfma_of(h, i, j, first and h == 0))
                 out.extend(side[n])
                 n += 1
+            if row_extra:
+                out.append(row_extra(h, i))
     return out
 
 
@@ -164,17 +166,19 @@ SWITCH = ["s_cmp_eq_u32 %[rem], 1",          # the last pair of K tiles prefetch
 
 
 def tile_asm(c, sched):
+    def kt(stage, first):
+        return ktile(c, stage, first, sched, lambda h, st: frag_reads(c, h, st), [ADVANCE[0:3], ADVANCE[3:6]],
+                     lambda h, i, j, fst: mfma(c, h, i, j, fst))
+
     t = []
     t += frag_reads(c, 0, 0)                 # K tile 0 landed and was waited for by the previous block / the prologue
     t += SWITCH
     t.append("s_waitcnt lgkmcnt(0)")
-    t += ktile(c, 0, True, sched)
-    t += ktile(c, 1, False, sched)
+    t += kt(0, True) + kt(1, False)
     t += ["s_sub_u32 %[rem], %[rem], 1", "s_cmp_eq_u32 %[rem], 0", "s_cbranch_scc1 L_a4_end_%="]
     t.append("L_a4_loop_%=:")
     t += SWITCH
-    t += ktile(c, 0, False, sched)
-    t += ktile(c, 1, False, sched)
+    t += kt(0, False) + kt(1, False)
     t += ["s_sub_u32 %[rem], %[rem], 1", "s_cmp_lg_u32 %[rem], 0", "s_cbranch_scc1 L_a4_loop_%="]
     t.append("L_a4_end_%=:")
     t += ["s_nop 7", "s_nop 7"]              # MFMA results -> the compiler's v_accvgpr_read (it cannot see into this block)
@@ -246,70 +250,21 @@ TN_SWITCH = (["s_cmp_eq_u32 %[rem], 1", "s_cbranch_scc0 L_tn_nosw_{u}_%=",
              + tn_clamp("%[ralo]", "%[rahi]", "s38") + tn_clamp("%[rblo]", "%[rbhi]", "s42") + ["L_tn_nosw_{u}_%=:"])
 
 
-def tn_ktile(c, stage, first, sched, duty):
-    nm = 64
-    side = [[] for _ in range(2 * nm)]
-    busy = [False] * (2 * nm)
-
-    def place(g, ins):
-        while busy[g]:
-            g += 1
-        busy[g] = True
-        side[g] += ins if isinstance(ins, list) else [ins]
-        return g
-
-    g = sched["read1_start"]
-    last_read = g
-    for ins in tn_frag_reads(1, stage):
-        last_read = place(g, ins)
-        g += sched["read_step"]
-    b1 = sched["b1_gap"]
-    assert last_read < b1
-    side[b1] += ["s_waitcnt lgkmcnt(0)", "s_barrier"]
-    b2 = nm + sched["b2_gap"]
-    g = b2 + 1
-    for ins in tn_frag_reads(0, stage ^ 1):
-        last_read = place(g, ins)
-        g += sched.get("read2_step", sched["read_step"])
-    assert last_read <= 2 * nm - 2, (last_read, 2 * nm)
-    side[2 * nm - 2].append("s_waitcnt lgkmcnt(0)")
-    ops = dma_ops(c, stage)
-    g = b1 + 2
-    m0_gap = b1 + 1
-    last_dma = b1
-    for m0, ld in ops:
-        side[m0_gap].append(m0)
-        at = place(max(g, m0_gap + 1), ld)
-        m0_gap = at + 1
-        last_dma = at
-        g = at + sched["dma_step"]
-    assert last_dma + 3 < 2 * nm, last_dma
-    side[last_dma + 1] += TN_ADVANCE_A
-    side[last_dma + 2] += TN_ADVANCE_B
-    issued = sum(1 for gg in range(b2) for ins in side[gg] if ins.startswith("buffer_load"))
-    side[b2].insert(0, f"s_waitcnt vmcnt({issued})")
-    side[b2].insert(1, "s_barrier")
-    out = []
-    n = 0
-    for h in range(2):
-        for i in range(8):
-            for j in range(8):
-                fa_, fb_ = fa(h, i), fb(h, j)
-                cc = "0" if (first and h == 0) else acc(c, i, j)
-                out.append(f"v_mfma_f32_16x16x32_bf16 {acc(c, i, j)}, {fa_}, {fb_}, {cc}")
-                out.extend(side[n])
-                n += 1
-            if duty:   # column sums of dY: A fragment x ones, into the compiler's VGPR accumulators
-                out.append(f"v_mfma_f32_16x16x32_bf16 %[bacc{i}], {fa(h, i)}, %[ones], %[bacc{i}]")
-    return out
-
-
 def tn_position(c, stage, first, sched, uid):
     """One K tile, in its two forms, and the bias-duty bookkeeping around them."""
+    def mfma_of(h, i, j, fst):   # srcA = the dY fragment: D[m][n]
+        return f"v_mfma_f32_16x16x32_bf16 {acc(c, i, j)}, {fa(h, i)}, {fb(h, j)}, {'0' if fst else acc(c, i, j)}"
+
+    def bias_mfma(h, i):         # column sums of dY: A fragment x ones, into the compiler's VGPR accumulators
+        return f"v_mfma_f32_16x16x32_bf16 %[bacc{i}], {fa(h, i)}, %[ones], %[bacc{i}]"
+
+    def kt(duty):                # (one gap stays free behind the two advances)
+        return ktile(c, stage, first, sched, tn_frag_reads, [TN_ADVANCE_A, TN_ADVANCE_B, []], mfma_of, bias_mfma if duty else None)
+
     t = ["s_cmp_eq_u32 %[bph], 0", f"s_cbranch_scc1 L_tn_duty_{uid}_%="]
-    t += tn_ktile(c, stage, first, sched, False)
+    t += kt(False)
     t += [f"s_branch L_tn_join_{uid}_%=", f"L_tn_duty_{uid}_%=:"]
-    t += tn_ktile(c, stage, first, sched, True)
+    t += kt(True)
     t += [f"L_tn_join_{uid}_%=:", "s_add_u32 %[bph], %[bph], 1", "s_cmp_eq_u32 %[bph], %[ntn]", "s_cselect_b32 %[bph], 0, %[bph]"]
     return t
 
@@ -341,6 +296,27 @@ def tn_prologue_asm(c):
         t += TN_ADVANCE_A + TN_ADVANCE_B
     t += [f"s_waitcnt vmcnt({c.ndma})", "s_barrier"]
     return t
+
+
+def operand_macros():
+    """The operand lists of the blocks above that are long and regular, so that gemm_a4.hip and gemm_tn_a4.hip do not type
+    them: the fragment registers as clobbers, the accumulators as outputs, the per-lane source offsets as inputs, and the
+    epilogue's v_permlane16_swap block over NJP column-block pairs (operand jp * 4 + e = xs[jp][e], then ys)."""
+    def rows(items, per_line, sep=", "):
+        return (sep.rstrip() + " \\\n  ").join(sep.join(items[k:k + per_line]) for k in range(0, len(items), per_line))
+
+    def define(head, body):
+        return f"#define {head} \\\n  {body}\n"
+
+    out = [define("STONK_A4_FRAG_CLOBBERS", rows([f'"v{n}"' for n in range(128, 256)], 16))]
+    for nacc in (16, 12):
+        out.append(define(f"STONK_A4_ACC_OUT_{nacc}(acc)", rows([f'"={{a[{16 * g}:{16 * g + 15}]}}"(acc[{g}])' for g in range(nacc)], 4)))
+    out.append(define("STONK_A4_VOFF_IN(voffA, voffB)", rows([f'[voff{x}{q}] "v"(voff{x}[{q}])' for x in "AB" for q in range(8)], 4)))
+    for njp in (4, 3):
+        swaps = ['"s_nop 1\\n"'] + [f'"v_permlane16_swap_b32 %{k}, %{k + 4 * njp}\\n"' for k in range(4 * njp)] + ['"s_nop 1"']
+        regs = [f'"+v"({a}[{jp}][{e}])' for a in ("xs", "ys") for jp in range(njp) for e in range(4)]
+        out.append(define(f"STONK_A4_SWAP_{njp}(xs, ys)", rows(swaps, 4, " ") + " \\\n  : " + rows(regs, 8)))
+    return out
 
 
 TN_SCHED = {"read1_start": 1, "read_step": 1, "b1_gap": 20, "dma_step": 6, "b2_gap": 30}
@@ -376,6 +352,8 @@ def generate(path, overrides=None):
                  "// %[bacc0..7] bias accumulators, %[ones] the all-ones operand; s48 scratch.\n")
     parts.append(emit("STONK_TN_A4_PROLOGUE", tn_prologue_asm(c)))
     parts.append(emit("STONK_TN_A4_TILE", tn_tile_asm(c, tn_sched)))
+    parts.append("// ---- operand lists of the blocks above and the epilogues' register-pair swap (both kernels)\n")
+    parts += operand_macros()
     text = "\n".join(parts)
     if path is None:
         return text
