@@ -92,11 +92,10 @@ __device__ __forceinline__ AttnBlock attn_block() {
   const int nx = gridDim.x, nh = gridDim.y;
   const int n = nx * nh * gridDim.z;
   const int lin = blockIdx.x + nx * (blockIdx.y + nh * blockIdx.z);
-  const int q = n >> 3, rm = n & 7, x = lin & 7;
-  int l = ((x < rm) ? x * (q + 1) : rm * (q + 1) + (x - rm) * q) + (lin >> 3);
+  int l = xcd_linear(lin, n);
   if (((nh * gridDim.z) & 7) == 0) {
     const int j = lin >> 3;
-    l = ((j / nx) * 8 + x) * nx + j % nx;
+    l = ((j / nx) * 8 + (lin & 7)) * nx + j % nx;
   }
   AttnBlock o;
   o.xb = l % nx;
@@ -205,9 +204,7 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(const AttnArgs p) {
 #pragma unroll
     for (int st = 0; st < 4; ++st) qf[st] = *(const bf16x8*)(qrow + 16 * st + 8 * hh);
   }
-  f32x16 o[2];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) o[0][i] = o[1][i] = 0.f;
+  f32x16 o[2] = {zero16(), zero16()};
   float m = NEG_INIT, l = 0.f;   // m in scaled log2 units
 
   const bf16* kbase = p.k + tok0 * p.ld + h * HD;
@@ -317,15 +314,7 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(const AttnArgs p) {
   }
   const float inv = (DROPOUT ? p.drop_scale : 1.f) / l;
   if (q0 + r >= nq) return;
-  bf16* orow = p.out + (tok0 + q0 + r) * p.ldo + h * HD;
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      bf16x4 v = {(bf16)(o[dt][4 * g] * inv), (bf16)(o[dt][4 * g + 1] * inv), (bf16)(o[dt][4 * g + 2] * inv),
-                  (bf16)(o[dt][4 * g + 3] * inv)};
-      *(bf16x4*)(orow + dt * 32 + 8 * g + 4 * hh) = v;
-    }
+  store_row(p.out + (tok0 + q0 + r) * p.ldo + h * HD, hh, [&](int dt, int i) { return o[dt][i] * inv; });
   if (hh == 0 && p.lse) p.lse[(long)(b * p.NH + h) * S + q0 + r] = (m + __builtin_amdgcn_logf(l)) * LN2;
 }
 
@@ -339,18 +328,9 @@ __global__ __launch_bounds__(128) void attn_delta_kernel(const AttnArgs p) {
   QUERY_EXTENT();
   const int q = blk.xb * 128 + threadIdx.x;
   if (q >= nq) return;
-  const bf16* drow = p.dout + (tok0 + q) * p.lddo + h * HD;
-  const bf16* orow = p.out + (tok0 + q) * p.ldo + h * HD;
-  // In the dQ kernel's order - its lane pair (r, hh) sums the 8-column chunks 2 st + hh, st = 0..3, then adds the two
-  // halves - so that the dK/dV kernel reads bitwise the same delta from either and the phases equal the single call.
-  float half[2] = {0.f, 0.f};
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    const bf16x8 d = *(const bf16x8*)(drow + 8 * c), o = *(const bf16x8*)(orow + 8 * c);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) half[c & 1] += (float)o[j] * (float)d[j];
-  }
-  p.delta[(long)(b * p.NH + h) * S + q] = half[0] + half[1];
+  // (in the dQ kernel's order: the dK/dV kernel reads bitwise the same delta from either and the phases equal the single call)
+  p.delta[(long)(b * p.NH + h) * S + q] =
+      delta_row(p.dout + (tok0 + q) * p.lddo + h * HD, p.out + (tok0 + q) * p.ldo + h * HD);
 }
 
 // ------------------------------------------------------------------ backward: dQ (query on the lane)
@@ -394,9 +374,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnArgs p) {
   const float lse_q = p.lse[stat - (q0 + r) + qr];
   // dS = P * (drop(dP) - delta) with drop(dP) = keep ? dP / (1-p) : 0  ==  (1/(1-p)) * P * ((keep ? dP : 0) - (1-p) delta)
   const float dlt_s = DROPOUT ? dlt / p.drop_scale : dlt;
-  f32x16 dq[2];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) dq[0][i] = dq[1][i] = 0.f;
+  f32x16 dq[2] = {zero16(), zero16()};
 
   const bf16* kbase = p.k + tok0 * p.ld + h * HD;
   const bf16* vbase = p.v + tok0 * p.ld + h * HD;
@@ -475,10 +453,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnArgs p) {
       }
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        float e[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) e[j] = s[8 * ks + j];
-        const bf16x8 dsf = pack8(e);
+        const bf16x8 dsf = acc_frag(s, ks);
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt) dq[dt] = mfma32(tr_frag(Ks, sub * 32 + 16 * ks, dt * 32, lane), dsf, dq[dt]);
       }
@@ -490,15 +465,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const AttnArgs p) {
   }
   const float fs = DROPOUT ? p.scale * p.drop_scale : p.scale;
   if (!qlive) return;
-  bf16* orow = p.dq + (tok0 + q0 + r) * p.ldd + h * HD;
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      bf16x4 v = {(bf16)(dq[dt][4 * g] * fs), (bf16)(dq[dt][4 * g + 1] * fs), (bf16)(dq[dt][4 * g + 2] * fs),
-                  (bf16)(dq[dt][4 * g + 3] * fs)};
-      *(bf16x4*)(orow + dt * 32 + 8 * g + 4 * hh) = v;
-    }
+  store_row(p.dq + (tok0 + q0 + r) * p.ldd + h * HD, hh, [&](int dt, int i) { return dq[dt][i] * fs; });
 }
 
 // ------------------------------------------------------------------ backward: dK, dV (key on the lane)
@@ -604,9 +571,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const AttnArgs p) 
         s[i] = mb;
         dp[i] = 0.f;
       }
-      // LDS operands are requested a phase ahead of the MFMAs that use them, and the scheduler is told to leave them
-      // there: left alone it sinks every read next to its MFMA (fewer live registers) and each of the tile's 32 MFMAs
-      // then waits out an LDS round trip - with two waves per SIMD nobody hides that (the loop was load / wait / MFMA).
       bf16x8 qa[4], da[4];
 #pragma unroll
       for (int st = 0; st < 4; ++st) {
@@ -619,7 +583,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const AttnArgs p) 
         s = mfma32(qa[st], kf[st], s);    // S[q][k] (+ key bias)
         dp = mfma32(da[st], vf[st], dp);  // dP[q][k] = sum_d dO[q][d] V[k][d]
       }
-      // the transposed operands of dV^T / dK^T: requested now, used after the softmax arithmetic below
       bf16x8 td[2][2], tq[2][2];
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks)
@@ -655,13 +618,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const AttnArgs p) 
       }
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        float e[8], f[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          e[j] = s[8 * ks + j];
-          f[j] = dp[8 * ks + j];
-        }
-        const bf16x8 pf = pack8(e), dsf = pack8(f);
+        const bf16x8 pf = acc_frag(s, ks), dsf = acc_frag(dp, ks);
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt) {
           dv[dt] = mfma32(td[ks][dt], pf, dv[dt]);   // dV^T += dO^T . P
@@ -690,7 +647,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(const AttnArgs p) 
     }
 }
 
-int check_common(const void* q, const void* k, const void* v, int64_t ld, int B, int NH, int S, int D) {
+// The argument checks of the forward and the backward entries, in one order. `ptrs` (STONK_EINVAL) and `aligned`
+// (STONK_EALIGN) are the entry's own conditions on its output pointers and row strides.
+int check_args(const void* q, const void* k, const void* v, int64_t ld, const int64_t* attention_mask, const int* seq_offsets,
+               const int* q_offsets, int B, int NH, int S, int D, float drop_p, bool ptrs, bool aligned) {
   STONK_CHECK_ARG(q && k && v, STONK_EINVAL);
   STONK_CHECK_ARG(D == HD, STONK_ESHAPE);
   // (the kernels keep one bit per 64-key tile of a sequence in a 64-bit word: 4096 keys)
@@ -698,7 +658,31 @@ int check_common(const void* q, const void* k, const void* v, int64_t ld, int B,
   STONK_CHECK_ARG(ld % 8 == 0, STONK_EALIGN);
   STONK_CHECK_ARG((uintptr_t)q % 16 == 0 && (uintptr_t)k % 16 == 0 && (uintptr_t)v % 16 == 0, STONK_EALIGN);
   STONK_CHECK_ARG((long)B * NH * S < (1L << 32), STONK_ESHAPE);  // 32-bit dropout row counter
+  STONK_CHECK_ARG(ptrs, STONK_EINVAL);
+  STONK_CHECK_ARG(!seq_offsets || attention_mask, STONK_EINVAL);   // packed rows carry their key mask
+  STONK_CHECK_ARG(!q_offsets || seq_offsets, STONK_EINVAL);
+  STONK_CHECK_ARG(aligned, STONK_EALIGN);
+  STONK_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f, STONK_EINVAL);
   return STONK_OK;
+}
+
+// the fields that the forward and the backward fill alike
+AttnArgs attn_args(const void* q, const void* k, const void* v, int64_t ld, const int64_t* attention_mask,
+                   const int* seq_offsets, const int* q_offsets, const void* out, int64_t ldo, const float* lse, int B, int NH,
+                   int S, float scale, float drop_p, uint32_t seed) {
+  AttnArgs a = {};
+  a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.ld = ld;
+  a.mask = (const long*)attention_mask; a.cu = seq_offsets; a.qoff = q_offsets;
+  a.out = (bf16*)out; a.ldo = ldo; a.lse = (float*)lse;
+  a.B = B; a.NH = NH; a.S = S; a.scale = scale;
+  a.drop_thr32 = stonk_drop_thr32(drop_p); a.drop_scale = 1.f / (1.f - drop_p); a.seed = stonk_seed_mix(seed);
+  return a;
+}
+
+// the runtime (mask, dropout) pair as the kernels' template arguments: f(HAS_MASK, DROPOUT)
+template <class F>
+void with_mask_dropout(const int64_t* attention_mask, float drop_p, F f) {
+  with_flag(attention_mask != nullptr, [&](auto hm) { with_flag(drop_p > 0.f, [&](auto dr) { f(hm, dr); }); });
 }
 
 }  // namespace
@@ -707,26 +691,16 @@ extern "C" int stonk_attention_fwd(const void* q, const void* k, const void* v, 
                                    const int64_t* attention_mask, const int* seq_offsets, const int* q_offsets, void* out,
                                    int64_t ldo, float* lse, int B, int NH, int S, int D, float scale, float drop_p,
                                    uint32_t seed, void* stream) {
-  int rc = check_common(q, k, v, ld, B, NH, S, D);
+  int rc = check_args(q, k, v, ld, attention_mask, seq_offsets, q_offsets, B, NH, S, D, drop_p, out && ldo % 4 == 0, true);
   if (rc) return rc;
-  STONK_CHECK_ARG(out && ldo % 4 == 0, STONK_EINVAL);
-  STONK_CHECK_ARG(!seq_offsets || attention_mask, STONK_EINVAL);   // packed rows carry their key mask
-  STONK_CHECK_ARG(!q_offsets || seq_offsets, STONK_EINVAL);
-  STONK_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f, STONK_EINVAL);
   if (B == 0) return STONK_OK;
-  AttnArgs a = {};
-  a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.ld = ld;
-  a.mask = (const long*)attention_mask; a.cu = seq_offsets; a.qoff = q_offsets; a.out = (bf16*)out; a.ldo = ldo; a.lse = lse;
-  a.B = B; a.NH = NH; a.S = S; a.scale = scale;
-  a.drop_thr32 = stonk_drop_thr32(drop_p); a.drop_scale = 1.f / (1.f - drop_p); a.seed = stonk_seed_mix(seed);
+  const AttnArgs a = attn_args(q, k, v, ld, attention_mask, seq_offsets, q_offsets, out, ldo, lse, B, NH, S, scale, drop_p, seed);
   const dim3 grid(S / 128, NH, B), block(256);
   hipStream_t st = (hipStream_t)stream;
-  const bool hm = attention_mask != nullptr, dr = drop_p > 0.f;
   const size_t kb = (size_t)S * sizeof(float);   // the sequence's key bias
-  if (hm && dr) hipLaunchKernelGGL((attn_fwd_kernel<true, true>), grid, block, kb, st, a);
-  else if (hm) hipLaunchKernelGGL((attn_fwd_kernel<true, false>), grid, block, kb, st, a);
-  else if (dr) hipLaunchKernelGGL((attn_fwd_kernel<false, true>), grid, block, 0, st, a);
-  else hipLaunchKernelGGL((attn_fwd_kernel<false, false>), grid, block, 0, st, a);
+  with_mask_dropout(attention_mask, drop_p, [&](auto hm, auto dr) {
+    hipLaunchKernelGGL((attn_fwd_kernel<hm(), dr()>), grid, block, hm() ? kb : 0, st, a);
+  });
   return stonk_launch_status();
 }
 
@@ -735,38 +709,23 @@ static int attention_bwd_launch(int phases, const void* q, const void* k, const 
                                 int64_t ldo, const void* dout, int64_t lddo, const float* lse, float* delta_ws, void* dq,
                                 void* dk, int64_t ldd, void* dv, int B, int NH, int S, int D, float scale, float drop_p,
                                 uint32_t seed, void* stream) {
-  int rc = check_common(q, k, v, ld, B, NH, S, D);
+  int rc = check_args(q, k, v, ld, attention_mask, seq_offsets, q_offsets, B, NH, S, D, drop_p,
+                      out && dout && lse && delta_ws && dq && dk && dv, ldo % 8 == 0 && lddo % 8 == 0 && ldd % 4 == 0);
   if (rc) return rc;
-  STONK_CHECK_ARG(out && dout && lse && delta_ws && dq && dk && dv, STONK_EINVAL);
-  STONK_CHECK_ARG(!seq_offsets || attention_mask, STONK_EINVAL);
-  STONK_CHECK_ARG(!q_offsets || seq_offsets, STONK_EINVAL);
-  STONK_CHECK_ARG(ldo % 8 == 0 && lddo % 8 == 0 && ldd % 4 == 0, STONK_EALIGN);
-  STONK_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f, STONK_EINVAL);
   if (B == 0) return STONK_OK;
-  AttnArgs a = {};
-  a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.ld = ld;
-  a.mask = (const long*)attention_mask; a.cu = seq_offsets; a.qoff = q_offsets; a.lse = (float*)lse; a.out = (bf16*)out; a.ldo = ldo;
+  AttnArgs a = attn_args(q, k, v, ld, attention_mask, seq_offsets, q_offsets, out, ldo, lse, B, NH, S, scale, drop_p, seed);
   a.dout = (const bf16*)dout; a.lddo = lddo; a.delta = delta_ws;
   a.dq = (bf16*)dq; a.dk = (bf16*)dk; a.dv = (bf16*)dv; a.ldd = ldd;
-  a.B = B; a.NH = NH; a.S = S; a.scale = scale;
-  a.drop_thr32 = stonk_drop_thr32(drop_p); a.drop_scale = 1.f / (1.f - drop_p); a.seed = stonk_seed_mix(seed);
   a.dq_writes_delta = phases == STONK_ATTN_BWD_ALL;   // (split calls: the DELTA phase produces it, before DQ and DKV)
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid(S / 128, NH, B), block(256);
-  const bool hm = attention_mask != nullptr, dr = drop_p > 0.f;
+  const size_t kb = (size_t)S * sizeof(float);
   if ((phases & STONK_ATTN_BWD_DELTA) && phases != STONK_ATTN_BWD_ALL)
     hipLaunchKernelGGL(attn_delta_kernel, grid, dim3(128), 0, st, a);
-#define LAUNCH_BWD(HM, DR)                                                                                         \
-  do {                                                                                                             \
-    if (phases & STONK_ATTN_BWD_DQ)                                                                                \
-      hipLaunchKernelGGL((attn_bwd_dq_kernel<HM, DR>), grid, block, HM ? (size_t)S * sizeof(float) : 0, st, a);    \
-    if (phases & STONK_ATTN_BWD_DKV) hipLaunchKernelGGL((attn_bwd_dkv_kernel<HM, DR>), grid, block, 0, st, a);     \
-  } while (0)
-  if (hm && dr) LAUNCH_BWD(true, true);
-  else if (hm) LAUNCH_BWD(true, false);
-  else if (dr) LAUNCH_BWD(false, true);
-  else LAUNCH_BWD(false, false);
-#undef LAUNCH_BWD
+  with_mask_dropout(attention_mask, drop_p, [&](auto hm, auto dr) {
+    if (phases & STONK_ATTN_BWD_DQ) hipLaunchKernelGGL((attn_bwd_dq_kernel<hm(), dr()>), grid, block, hm() ? kb : 0, st, a);
+    if (phases & STONK_ATTN_BWD_DKV) hipLaunchKernelGGL((attn_bwd_dkv_kernel<hm(), dr()>), grid, block, 0, st, a);
+  });
   return stonk_launch_status();
 }
 

@@ -25,18 +25,12 @@
 // 128-byte lines). `modal_mass` is summed per lane over the tiles of each half in tile order and merged across the lane
 // groups by two xor shuffles: no atomics, bitwise reproducible.
 #include "common.h"
+#include "attn_tiles.h"   // the K tile image and its swizzle, the score-bias constants, the XCD map
 
 namespace {
 
-constexpr int HD = 64;        // head dim
-constexpr int TK = 64;        // keys per LDS tile
-constexpr int ROWB = 128;     // bytes per tile row
-constexpr int TILEB = TK * ROWB;
 constexpr int QB = 128;       // queries per workgroup: 4 waves x 2 groups of 16
 constexpr int PLD = TK + 4;   // floats per row of a wave's probability tile (272 bytes: 16 rows two-way at worst)
-constexpr float LOG2E = 1.4426950408889634f;
-constexpr float NEG_MASK = -0x1p100f;   // raw-score bias of a masked key (attention.hip)
-constexpr float NEG_INIT = -0x1p120f;
 
 struct ProbsArgs {
   const bf16* q;
@@ -48,16 +42,6 @@ struct ProbsArgs {
   int NH, S, half;
   float scale;
 };
-
-// 16-byte chunk swizzle of a 128-byte tile row, as attention.hip: 16 consecutive rows reading one logical chunk
-// (ds_read_b128 fragments) hit 16 different bank groups.
-__device__ __forceinline__ int swz(int row) {
-  const int t = (row >> 1) & 7;
-  return ((t & 1) << 2) | (t >> 1);
-}
-__device__ __forceinline__ int tile_off(int row, int col) {
-  return row * ROWB + ((((col >> 3) ^ swz(row)) << 4) | ((col & 7) << 1));
-}
 
 __device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
@@ -71,13 +55,8 @@ __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// Workgroup -> (query block, head, sequence): every XCD takes one contiguous run of the linear order (workgroups are
-// dispatched round-robin over the 8 XCDs), so the S/128 blocks of a head read its K through one L2.
-__device__ __forceinline__ int xcd_linear(int lin, int n) {
-  const int q = n >> 3, rm = n & 7, x = lin & 7;
-  return ((x < rm) ? x * (q + 1) : rm * (q + 1) + (x - rm) * q) + (lin >> 3);
-}
-
+// Workgroup -> (query block, head, sequence) through xcd_linear(): every XCD takes one contiguous run of the linear
+// order, so the S/128 blocks of a head read its K through one L2.
 template <bool STORE_P>
 __global__ __launch_bounds__(256, 2) void attn_probs_kernel(const ProbsArgs p) {
   __shared__ __attribute__((aligned(16))) char kt_lds[2 * TILEB];
@@ -108,21 +87,15 @@ __global__ __launch_bounds__(256, 2) void attn_probs_kernel(const ProbsArgs p) {
   // K tiles: 64 rows x 128 bytes = 512 16-byte chunks over 256 threads, fetched one tile ahead
   const bf16* kbase = p.k + tok0 * p.ld + h * HD;
   const int ntiles = S / TK, nit = 2 * ntiles;
-  bf16x8 stage[2];
+  Stage2 stage;
   auto load_tile = [&](int kt) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int id = tid + 256 * i;
-      stage[i] = *(const bf16x8*)(kbase + (long)(kt * TK + (id >> 3)) * p.ld + (id & 7) * 8);
+      stage.c[i] = *(const bf16x8*)(kbase + (long)(kt * TK + (id >> 3)) * p.ld + (id & 7) * 8);
     }
   };
-  auto store_tile = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int id = tid + 256 * i;
-      *(bf16x8*)(kt_lds + buf * TILEB + tile_off(id >> 3, (id & 7) * 8)) = stage[i];
-    }
-  };
+  auto store_tile = [&](int buf) { stage_store(stage, kt_lds + buf * TILEB, tid); };
   load_tile(0);
   store_tile(0);
   __syncthreads();   // (also publishes kbias)

@@ -1,7 +1,11 @@
-// Tile helpers shared by the dense attention kernels (attention.hip) and the block-sparse ones (bigbird_attention.hip):
-// the [64][64] bf16 LDS tile image and its swizzle, the MFMA fragments read from it, the register-staged tile loads,
-// the packed fp32 / bf16 arithmetic and the score-bias constants. Each including file gets its own (internal) copy.
+// Tile helpers shared by the dense attention kernels (attention.hip), the block-sparse ones (bigbird_attention.hip) and
+// the written-out probabilities (attention_probs.hip): the [64][64] bf16 LDS tile image and its swizzle, the MFMA
+// fragments read from it, the register-staged tile loads, the packed fp32 / bf16 arithmetic, the score-bias constants, the
+// accumulator conversions and row stores, the XCD map and the delta row sum. Each including file gets its own (internal)
+// copy. A helper is used only where the kernel compiles to the instructions of its written-out form
+// (profiles/refactor_attention_sources.md lists, per helper, the kernels that keep their own lines for that reason).
 #pragma once
+#include <type_traits>
 #include "common.h"
 
 namespace {
@@ -156,5 +160,73 @@ __device__ __forceinline__ void stage_store(const Stage2& s, char* tile, int tid
 #else
 #define TILE_BARRIER() __syncthreads()
 #endif
+
+// A zeroed accumulator, and the score accumulator's initial value: the bias of this lane's 16 keys (Mb: the 32 keys of its
+// MFMA tile), zeros without a mask
+__device__ __forceinline__ f32x16 zero16() {
+  f32x16 z;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) z[i] = 0.f;
+  return z;
+}
+template <bool HAS_MASK>
+__device__ __forceinline__ f32x16 score_bias(const float* Mb, int hh) {
+  f32x16 s;
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    f32x4 mb = {0.f, 0.f, 0.f, 0.f};
+    if (HAS_MASK) mb = *(const f32x4*)(Mb + 8 * g + 4 * hh);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s[4 * g + j] = mb[j];
+  }
+  return s;
+}
+
+// registers 8 ks .. 8 ks + 7 of an accumulator tile as the B operand of the next MFMA
+__device__ __forceinline__ bf16x8 acc_frag(const f32x16& s, int ks) {
+  float e[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) e[j] = s[8 * ks + j];
+  return pack8(e);
+}
+
+// A lane's output row: val(dt, i) = the final value of register i of its accumulator for columns 32 dt .. + 31, as bf16
+template <class F>
+__device__ __forceinline__ void store_row(bf16* row, int hh, F val) {
+#pragma unroll
+  for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      bf16x4 v = {(bf16)val(dt, 4 * g), (bf16)val(dt, 4 * g + 1), (bf16)val(dt, 4 * g + 2), (bf16)val(dt, 4 * g + 3)};
+      *(bf16x4*)(row + dt * 32 + 8 * g + 4 * hh) = v;
+    }
+}
+
+// Workgroups are dispatched round-robin over the 8 XCDs: the place of workgroup `lin` of n in an order where every XCD
+// takes one contiguous run (a bijection of [0, n)), so that neighbours in that order share an L2
+__device__ __forceinline__ int xcd_linear(int lin, int n) {
+  const int q = n >> 3, rm = n & 7, x = lin & 7;
+  return ((x < rm) ? x * (q + 1) : rm * (q + 1) + (x - rm) * q) + (lin >> 3);
+}
+
+// delta = rowsum(dO * O) of one 64-column row, in the dQ kernel's order - its lane pair (r, hh) sums the 8-column chunks
+// 2 st + hh, st = 0..3, then adds the two halves - so that every producer of delta gives bitwise the same
+__device__ __forceinline__ float delta_row(const bf16* drow, const bf16* orow) {
+  float half[2] = {0.f, 0.f};
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    const bf16x8 d = *(const bf16x8*)(drow + 8 * c), o = *(const bf16x8*)(orow + 8 * c);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) half[c & 1] += (float)o[j] * (float)d[j];
+  }
+  return half[0] + half[1];
+}
+
+// host side: a runtime flag as a template argument - f gets std::true_type or std::false_type
+template <class F>
+void with_flag(bool on, F f) {
+  if (on) f(std::true_type{});
+  else f(std::false_type{});
+}
 
 }  // namespace

@@ -150,9 +150,7 @@ __global__ __launch_bounds__(256, 2) void bb_fwd_kernel(const BbArgs p) {
 #pragma unroll
     for (int st = 0; st < 4; ++st) qf[st] = *(const bf16x8*)(qrow + 16 * st + 8 * hh);
   }
-  f32x16 o[2];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) o[0][i] = o[1][i] = 0.f;
+  f32x16 o[2] = {zero16(), zero16()};
   float m = NEG_INIT, l = 0.f;   // m in scaled log2 units
 
   const bf16* kbase = p.k + tok0 * p.ld + h * HD;
@@ -184,14 +182,7 @@ __global__ __launch_bounds__(256, 2) void bb_fwd_kernel(const BbArgs p) {
     if (more) load_tile(lj[it + 1]);
     const float mu = (float)lm[it];
     // S^T = K . Q^T (+ key bias through the accumulator) for this wave's 32 keys of the tile, raw units
-    f32x16 s;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      f32x4 mb = {0.f, 0.f, 0.f, 0.f};
-      if (HAS_MASK) mb = *(const f32x4*)(Mb + 8 * g + 4 * hh);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) s[4 * g + j] = mb[j];
-    }
+    f32x16 s = score_bias<HAS_MASK>(Mb, hh);
 #pragma unroll
     for (int st = 0; st < 4; ++st) s = mfma32(row_frag(Ks, kh * 32, st, r, hh), qf[st], s);
     float tmax = max16_mfma(s);
@@ -226,10 +217,7 @@ __global__ __launch_bounds__(256, 2) void bb_fwd_kernel(const BbArgs p) {
     // O^T += V^T . (m P)^T
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      float e[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) e[j] = s[8 * ks + j];
-      const bf16x8 pf = pack8(e);
+      const bf16x8 pf = acc_frag(s, ks);
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt) o[dt] = mfma32(tr_frag(Vs, kh * 32 + 16 * ks, dt * 32, lane), pf, o[dt]);
     }
@@ -268,7 +256,7 @@ __global__ __launch_bounds__(256, 2) void bb_fwd_kernel(const BbArgs p) {
 }
 
 // ------------------------------------------------------------------ backward: per-row statistics
-// delta = rowsum(dO * O) (in the dense delta kernel's summation order) and -lse in log2 units - for a row whose listed keys
+// delta = rowsum(dO * O) (delta_row: the one summation order of every producer of delta) and -lse in log2 units - for a row whose listed keys
 // are all masked -log2(64 L) instead, L = the total multiplicity of its block's list (see the head of the file).
 __global__ __launch_bounds__(128) void bb_prep_kernel(const BbArgs p) {
   const long rows = (long)p.B * p.NH * p.S;
@@ -279,16 +267,7 @@ __global__ __launch_bounds__(128) void bb_prep_kernel(const BbArgs p) {
   const long bh = idx / S;
   const int h = (int)(bh % p.NH);
   const long tok = (bh / p.NH) * S + qrow;
-  const bf16* drow = p.dout + tok * p.lddo + h * HD;
-  const bf16* orow = p.out + tok * p.ldo + h * HD;
-  float half[2] = {0.f, 0.f};
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    const bf16x8 d = *(const bf16x8*)(drow + 8 * c), o = *(const bf16x8*)(orow + 8 * c);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) half[c & 1] += (float)o[j] * (float)d[j];
-  }
-  p.ws[idx] = half[0] + half[1];
+  p.ws[idx] = delta_row(p.dout + tok * p.lddo + h * HD, p.out + tok * p.ldo + h * HD);
   const float lse = p.lse[idx];
   float nls = -lse * LOG2E;
   if (bb_degenerate(lse, p.scale)) {
@@ -336,9 +315,7 @@ __global__ __launch_bounds__(256, 2) void bb_bwd_dq_kernel(const BbArgs p) {
   const long rows = (long)p.B * p.NH * S;
   const float dlt = p.ws[stat], nlse2 = p.ws[rows + stat];
   const float sc2 = bb_degenerate(p.lse[stat], p.scale) ? 0.f : p.scale * LOG2E;   // (a zero score scale: P = 2^nlse2 for every key)
-  f32x16 dq[2];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) dq[0][i] = dq[1][i] = 0.f;
+  f32x16 dq[2] = {zero16(), zero16()};
 
   const bf16* kbase = p.k + tok0 * p.ld + h * HD;
   const bf16* vbase = p.v + tok0 * p.ld + h * HD;
@@ -368,17 +345,7 @@ __global__ __launch_bounds__(256, 2) void bb_bwd_dq_kernel(const BbArgs p) {
     const bool more = it + 1 < nlist;
     if (more) load_tile(lj[it + 1]);
     const float mu = (float)lm[it];
-    f32x16 s, dp;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      f32x4 mb = {0.f, 0.f, 0.f, 0.f};
-      if (HAS_MASK) mb = *(const f32x4*)(Mb + 8 * g + 4 * hh);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        s[4 * g + j] = mb[j];
-        dp[4 * g + j] = 0.f;
-      }
-    }
+    f32x16 s = score_bias<HAS_MASK>(Mb, hh), dp = zero16();
 #pragma unroll
     for (int st = 0; st < 4; ++st) {
       s = mfma32(row_frag(Ks, kh * 32, st, r, hh), qf[st], s);      // S^T[k][q] (+ key bias)
@@ -395,10 +362,7 @@ __global__ __launch_bounds__(256, 2) void bb_bwd_dq_kernel(const BbArgs p) {
     }
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      float e[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) e[j] = s[8 * ks + j];
-      const bf16x8 dsf = pack8(e);
+      const bf16x8 dsf = acc_frag(s, ks);
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt) dq[dt] = mfma32(tr_frag(Ks, kh * 32 + 16 * ks, dt * 32, lane), dsf, dq[dt]);
     }
@@ -415,17 +379,8 @@ __global__ __launch_bounds__(256, 2) void bb_bwd_dq_kernel(const BbArgs p) {
   }
   __syncthreads();
   if (kh == 1) return;
-  bf16* orow = p.dq + (tok0 + q0 + r) * p.ldd + h * HD;
-#pragma unroll
-  for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      float e[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) e[j] = (dq[dt][4 * g + j] + xw[(dt * 16 + 4 * g + j) * 64]) * p.scale;
-      bf16x4 v = {(bf16)e[0], (bf16)e[1], (bf16)e[2], (bf16)e[3]};
-      *(bf16x4*)(orow + dt * 32 + 8 * g + 4 * hh) = v;
-    }
+  store_row(p.dq + (tok0 + q0 + r) * p.ldd + h * HD, hh,
+            [&](int dt, int i) { return (dq[dt][i] + xw[(dt * 16 + i) * 64]) * p.scale; });
 }
 
 // ------------------------------------------------------------------ backward: dK, dV (key on the lane)
@@ -512,7 +467,7 @@ __global__ __launch_bounds__(256, 2) void bb_bwd_dkv_kernel(const BbArgs p) {
         s[i] = mb;
         dp[i] = 0.f;
       }
-      // (operands requested a phase ahead of the MFMAs that use them, as in the dense dK/dV kernel)
+      // (operands requested a phase ahead of the MFMAs that use them and held there: see attn_bwd_dkv_kernel)
       bf16x8 qa[4], da[4];
 #pragma unroll
       for (int st = 0; st < 4; ++st) {
@@ -553,13 +508,7 @@ __global__ __launch_bounds__(256, 2) void bb_bwd_dkv_kernel(const BbArgs p) {
       }
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        float e[8], f[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          e[j] = s[8 * ks + j];
-          f[j] = dp[8 * ks + j];
-        }
-        const bf16x8 pf = pack8(e), dsf = pack8(f);
+        const bf16x8 pf = acc_frag(s, ks), dsf = acc_frag(dp, ks);
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt) {
           dv[dt] = mfma32(td[ks][dt], pf, dv[dt]);   // dV^T += dO^T . (m P)
@@ -619,6 +568,18 @@ int bb_check_common(const void* q, const void* k, const void* v, int64_t ld, con
   return STONK_OK;
 }
 
+// the fields that the forward and the backward fill alike
+BbArgs bb_args(const void* q, const void* k, const void* v, int64_t ld, const int64_t* attention_mask, const int* key_blocks,
+               const int* key_mult, const int* key_count, const void* out, int64_t ldo, const float* lse, int B, int NH, int S,
+               float scale, int* err_flag) {
+  BbArgs a = {};
+  a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.ld = ld;
+  a.mask = (const long*)attention_mask; a.kb = key_blocks; a.km = key_mult; a.kc = key_count;
+  a.out = (bf16*)out; a.ldo = ldo; a.lse = (float*)lse;
+  a.B = B; a.NH = NH; a.S = S; a.nb = S / TK; a.scale = scale; a.err = err_flag;
+  return a;
+}
+
 }  // namespace
 
 extern "C" int stonk_block_sparse_attention_fwd(const void* q, const void* k, const void* v, int64_t ld,
@@ -631,15 +592,10 @@ extern "C" int stonk_block_sparse_attention_fwd(const void* q, const void* k, co
   STONK_CHECK_ARG(ldo >= (long)NH * HD, STONK_ESHAPE);
   STONK_CHECK_ARG(ldo % 4 == 0 && (uintptr_t)out % 8 == 0, STONK_EALIGN);
   if (B == 0) return STONK_OK;
-  BbArgs a = {};
-  a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.ld = ld;
-  a.mask = (const long*)attention_mask; a.kb = key_blocks; a.km = key_mult; a.kc = key_count;
-  a.out = (bf16*)out; a.ldo = ldo; a.lse = lse;
-  a.B = B; a.NH = NH; a.S = S; a.nb = S / TK; a.scale = scale; a.err = err_flag;
+  const BbArgs a = bb_args(q, k, v, ld, attention_mask, key_blocks, key_mult, key_count, out, ldo, lse, B, NH, S, scale, err_flag);
   const dim3 grid(B * NH * a.nb), block(256);
   hipStream_t st = (hipStream_t)stream;
-  if (attention_mask) hipLaunchKernelGGL((bb_fwd_kernel<true>), grid, block, 0, st, a);
-  else hipLaunchKernelGGL((bb_fwd_kernel<false>), grid, block, 0, st, a);
+  with_flag(attention_mask != nullptr, [&](auto hm) { hipLaunchKernelGGL((bb_fwd_kernel<hm()>), grid, block, 0, st, a); });
   return stonk_launch_status();
 }
 
@@ -658,23 +614,17 @@ extern "C" int stonk_block_sparse_attention_bwd(const void* q, const void* k, co
   STONK_CHECK_ARG((uintptr_t)out % 16 == 0 && (uintptr_t)dout % 16 == 0, STONK_EALIGN);
   STONK_CHECK_ARG((uintptr_t)dq % 8 == 0 && (uintptr_t)dk % 8 == 0 && (uintptr_t)dv % 8 == 0, STONK_EALIGN);
   if (B == 0) return STONK_OK;
-  BbArgs a = {};
-  a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.ld = ld;
-  a.mask = (const long*)attention_mask; a.kb = key_blocks; a.km = key_mult; a.kc = key_count;
+  BbArgs a = bb_args(q, k, v, ld, attention_mask, key_blocks, key_mult, key_count, out, ldo, lse, B, NH, S, scale, err_flag);
   a.qb = query_blocks; a.qm = query_mult; a.qc = query_count;
-  a.out = (bf16*)out; a.ldo = ldo; a.lse = (float*)lse; a.dout = (const bf16*)dout; a.lddo = lddo; a.ws = delta_ws;
+  a.dout = (const bf16*)dout; a.lddo = lddo; a.ws = delta_ws;
   a.dq = (bf16*)dq; a.dk = (bf16*)dk; a.dv = (bf16*)dv; a.ldd = ldd;
-  a.B = B; a.NH = NH; a.S = S; a.nb = S / TK; a.scale = scale; a.err = err_flag;
   const dim3 grid(B * NH * a.nb), block(256);
   const long rows = (long)B * NH * S;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(bb_prep_kernel, dim3((unsigned)((rows + 127) / 128)), dim3(128), 0, st, a);
-  if (attention_mask) {
-    hipLaunchKernelGGL((bb_bwd_dq_kernel<true>), grid, block, 0, st, a);
-    hipLaunchKernelGGL((bb_bwd_dkv_kernel<true>), grid, block, 0, st, a);
-  } else {
-    hipLaunchKernelGGL((bb_bwd_dq_kernel<false>), grid, block, 0, st, a);
-    hipLaunchKernelGGL((bb_bwd_dkv_kernel<false>), grid, block, 0, st, a);
-  }
+  with_flag(attention_mask != nullptr, [&](auto hm) {
+    hipLaunchKernelGGL((bb_bwd_dq_kernel<hm()>), grid, block, 0, st, a);
+    hipLaunchKernelGGL((bb_bwd_dkv_kernel<hm()>), grid, block, 0, st, a);
+  });
   return stonk_launch_status();
 }

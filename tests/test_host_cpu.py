@@ -455,9 +455,11 @@ def test_written_out_kernels_use_no_scratch():
     assert not bad, bad
     tn = kr.kernel_resources(os.path.join(csrc, "gemm_tn_a4.o"))
     assert [k["scratch"] <= 272 for k in tn] == [True]
-    attn = kr.kernel_resources(os.path.join(csrc, "attention.o"))
-    bad = [(k["name"], k["scratch"]) for k in attn if k["scratch"] or k.get("vgpr_spill", 0)]
-    assert len(attn) == 13 and not bad, bad
+    # (the three attention objects share attn_tiles.h with kernels that run at 240 to 256 registers)
+    for obj, count in (("attention.o", 13), ("bigbird_attention.o", 7), ("attention_probs.o", 2)):
+        attn = kr.kernel_resources(os.path.join(csrc, obj))
+        bad = [(k["name"], k["scratch"]) for k in attn if k["scratch"] or k.get("vgpr_spill", 0) or k.get("sgpr_spill", 0)]
+        assert len(attn) == count and not bad, (obj, len(attn), bad)
 
 
 def test_generated_gemm_loop_is_up_to_date():
