@@ -18,6 +18,11 @@ What it is: a plain-PyTorch fp32 restatement (no ``transformers`` import, no ref
   * the offline masking that defines the batch schema
     ref:src/stonkgs/data/indra_for_pretraining.py:33-77 (replace_mlm_tokens), :80-126 (NSP negatives).
 
+Dropout: off by default (every `dropout=None`: no operation is added, the golden vectors are replayed bit for bit). With a
+mask provider (`_drop`; tests/step_dropout_ref.py) the keep-masks are multiplied in where hf drops and the engine does:
+behind both embeddings LayerNorms, on the softmax probabilities, on the two output projections before their residual, on
+the pooled vector before the classifier - torch autograd then gives the exact gradients of a step under THOSE masks.
+
 Pinning: the reference's own test-suite holds no vectors for this path, so the oracle is
 pinned against the reference ITSELF, imported in the authoring container by ``oracle/make_golden.py`` (reference
 ``forward`` unmodified + HF BERT, local config, random weights); the resulting inputs/outputs are committed under
@@ -94,8 +99,38 @@ def _linear(x: Tensor, sd: Dict[str, Tensor], prefix: str) -> Tensor:
     return F.linear(x, sd[prefix + ".weight"], sd.get(prefix + ".bias"))
 
 
-def bert_embeddings(sd, prefix, cfg, *, input_ids=None, inputs_embeds=None, token_type_ids=None) -> Tensor:
-    """hf BertEmbeddings.forward :98-108 (absolute positions, dropout p=0 / eval)."""
+class _MaskMul(torch.autograd.Function):
+    """y = x * fwd, dx = dy * bwd. The two masks are one tensor in normal use; a test that wants to know what a backward
+    with ANOTHER mask than the forward's would compute hands in two."""
+
+    @staticmethod
+    def forward(ctx, x, fwd, bwd):
+        ctx.save_for_backward(bwd)
+        return x * fwd
+
+    @staticmethod
+    def backward(ctx, g):
+        (bwd,) = ctx.saved_tensors
+        return g * bwd, None, None
+
+
+def _drop(x: Tensor, dropout, site_key) -> Tensor:
+    """Dropout at the site `site_key` = (HF module prefix, site): 0 = behind an embeddings LayerNorm / on the pooled
+    vector, 1 = the softmax probabilities, 2 = attention.output.dense, 3 = output.dense.
+    `dropout` None: x itself (p = 0, no operation added). Else an object with `keep(site_key, shape) -> Tensor`, the {0, 1}
+    keep-mask already scaled by 1 / (1 - float32(p)) (tests/step_dropout_ref.py derives it from the engine's seed and row
+    contract and oracle/dropout_oracle.py); an optional `keep_backward(site_key, shape)` gives the mask of the backward."""
+    if dropout is None:
+        return x
+    dt = torch.promote_types(x.dtype, torch.float32)   # (under autocast x may be bf16: the product is taken in fp32)
+    fwd = dropout.keep(site_key, tuple(x.shape)).to(dt)
+    kb = getattr(dropout, "keep_backward", None)
+    bwd = fwd if kb is None else kb(site_key, tuple(x.shape)).to(dt)
+    return _MaskMul.apply(x, fwd, bwd)
+
+
+def bert_embeddings(sd, prefix, cfg, *, input_ids=None, inputs_embeds=None, token_type_ids=None, dropout=None) -> Tensor:
+    """hf BertEmbeddings.forward :98-108 (absolute positions; `dropout` None: p = 0 / eval, else see `_drop`)."""
     if inputs_embeds is None:
         inputs_embeds = sd[prefix + ".word_embeddings.weight"][input_ids]
     B, S = inputs_embeds.shape[:2]
@@ -103,10 +138,12 @@ def bert_embeddings(sd, prefix, cfg, *, input_ids=None, inputs_embeds=None, toke
         token_type_ids = torch.zeros(B, S, dtype=torch.long)
     pos = sd[prefix + ".position_embeddings.weight"][:S][None]
     typ = sd[prefix + ".token_type_embeddings.weight"][token_type_ids]
-    return _ln(inputs_embeds + typ + pos, sd, prefix + ".LayerNorm", cfg.layer_norm_eps)
+    return _drop(_ln(inputs_embeds + typ + pos, sd, prefix + ".LayerNorm", cfg.layer_norm_eps), dropout, (prefix, 0))
 
 
-def bert_layer(x: Tensor, sd, prefix: str, cfg: OracleConfig, mask_bias: Optional[Tensor]) -> Tensor:
+def bert_layer(x: Tensor, sd, prefix: str, cfg: OracleConfig, mask_bias: Optional[Tensor], dropout=None) -> Tensor:
+    """hf BertLayer. Dropout (`_drop`) where hf has it: on the softmax probabilities (BertSelfAttention :195) and on
+    dense(x) + bias of BertSelfOutput :291 / BertOutput :349, before the residual is added."""
     B, S, H = x.shape
     nh = cfg.num_attention_heads
     d = H // nh
@@ -120,28 +157,31 @@ def bert_layer(x: Tensor, sd, prefix: str, cfg: OracleConfig, mask_bias: Optiona
     scores = q @ k.transpose(-1, -2) / math.sqrt(d)
     if mask_bias is not None:
         scores = scores + mask_bias
-    ctx = (torch.softmax(scores, dim=-1) @ v).transpose(1, 2).reshape(B, S, H)
-    h1 = _ln(_linear(ctx, sd, prefix + ".attention.output.dense") + x, sd, prefix + ".attention.output.LayerNorm",
-             cfg.layer_norm_eps)
+    ctx = (_drop(torch.softmax(scores, dim=-1), dropout, (prefix, 1)) @ v).transpose(1, 2).reshape(B, S, H)
+    h1 = _ln(_drop(_linear(ctx, sd, prefix + ".attention.output.dense"), dropout, (prefix, 2)) + x, sd,
+             prefix + ".attention.output.LayerNorm", cfg.layer_norm_eps)
     inter = F.gelu(_linear(h1, sd, prefix + ".intermediate.dense"))  # exact erf GELU (hidden_act="gelu")
-    return _ln(_linear(inter, sd, prefix + ".output.dense") + h1, sd, prefix + ".output.LayerNorm", cfg.layer_norm_eps)
+    return _ln(_drop(_linear(inter, sd, prefix + ".output.dense"), dropout, (prefix, 3)) + h1, sd,
+               prefix + ".output.LayerNorm", cfg.layer_norm_eps)
 
 
-def bert_encoder(x, sd, prefix, cfg, n_layers, attention_mask=None, collect: Optional[list] = None) -> Tensor:
+def bert_encoder(x, sd, prefix, cfg, n_layers, attention_mask=None, collect: Optional[list] = None,
+                 dropout=None) -> Tensor:
     mask_bias = None
     if attention_mask is not None:  # additive key-padding mask [B,1,1,S]
         mask_bias = (1.0 - attention_mask[:, None, None, :].to(x.dtype)) * torch.finfo(x.dtype).min
     for i in range(n_layers):
-        x = bert_layer(x, sd, f"{prefix}.layer.{i}", cfg, mask_bias)
+        x = bert_layer(x, sd, f"{prefix}.layer.{i}", cfg, mask_bias, dropout)
         if collect is not None:
             collect.append(x)
     return x
 
 
-def lm_backbone_forward(sd, cfg: OracleConfig, input_ids: Tensor) -> Tensor:
-    """`self.lm_backbone(ids)[0]`: full BERT forward, NO attention mask (quirk Q5, ref:stonkgs_model.py:178)."""
-    x = bert_embeddings(sd, "lm_backbone.embeddings", cfg, input_ids=input_ids)
-    return bert_encoder(x, sd, "lm_backbone.encoder", cfg, cfg.n_backbone_layers)
+def lm_backbone_forward(sd, cfg: OracleConfig, input_ids: Tensor, dropout=None) -> Tensor:
+    """`self.lm_backbone(ids)[0]`: full BERT forward, NO attention mask (quirk Q5, ref:stonkgs_model.py:178). In training
+    mode its dropout is live although it is frozen (quirk Q6): `dropout` reaches every site of it."""
+    x = bert_embeddings(sd, "lm_backbone.embeddings", cfg, input_ids=input_ids, dropout=dropout)
+    return bert_encoder(x, sd, "lm_backbone.encoder", cfg, cfg.n_backbone_layers, dropout=dropout)
 
 
 def special_vectors(sd, cfg: OracleConfig) -> Dict[int, Tensor]:
@@ -150,25 +190,34 @@ def special_vectors(sd, cfg: OracleConfig) -> Dict[int, Tensor]:
 
 
 # --------------------------------------------------------------------------------------------- the hot function
+def _embeds_dtype(token_embeddings: Tensor) -> torch.dtype:
+    """fp32, as the reference casts the concatenation (ref:stonkgs_model.py:193-200) - unless the oracle is run in fp64 as a
+    whole (fp64 weights: a higher-precision yardstick for the tests), which then stays fp64."""
+    return torch.float64 if token_embeddings.dtype == torch.float64 else torch.float32
+
+
 def forward(sd: Dict[str, Tensor], cfg: OracleConfig, kg_table: Tensor, input_ids: Tensor,
             attention_mask: Optional[Tensor] = None, token_type_ids: Optional[Tensor] = None,
             masked_lm_labels: Optional[Tensor] = None, ent_masked_lm_labels: Optional[Tensor] = None,
-            next_sentence_labels: Optional[Tensor] = None, collect_layers: bool = False) -> Dict[str, Tensor]:
-    """ref:src/stonkgs/models/stonkgs_model.py:149-258, step numbers as in SURVEY.md section 3.2."""
+            next_sentence_labels: Optional[Tensor] = None, collect_layers: bool = False,
+            dropout=None) -> Dict[str, Tensor]:
+    """ref:src/stonkgs/models/stonkgs_model.py:149-258, step numbers as in SURVEY.md section 3.2. `dropout`: see `_drop`
+    (the pooler and the head transform have none)."""
     half = cfg.half_length
     # 1. frozen LM backbone on the text half
-    token_embeddings = lm_backbone_forward(sd, cfg, input_ids[:, :half])
+    token_embeddings = lm_backbone_forward(sd, cfg, input_ids[:, :half], dropout)
     # 2. KG gather (KeyError for ids outside the table, like the reference's dict lookup)
     ent_ids = input_ids[:, half:]
     if ent_ids.numel() and (int(ent_ids.min()) < 0 or int(ent_ids.max()) >= kg_table.shape[0]):
         raise KeyError(int(ent_ids.max()))
     ent_embeddings = kg_table[ent_ids]
     # 3. concat, fp32
-    inputs_embeds = torch.cat([token_embeddings, ent_embeddings], dim=1).to(torch.float32)
+    inputs_embeds = torch.cat([token_embeddings, ent_embeddings], dim=1).to(_embeds_dtype(token_embeddings))
     # 4. trainable encoder + pooler
-    emb = bert_embeddings(sd, "bert.embeddings", cfg, inputs_embeds=inputs_embeds, token_type_ids=token_type_ids)
+    emb = bert_embeddings(sd, "bert.embeddings", cfg, inputs_embeds=inputs_embeds, token_type_ids=token_type_ids,
+                          dropout=dropout)
     layers: Optional[list] = [] if collect_layers else None
-    seq = bert_encoder(emb, sd, "bert.encoder", cfg, cfg.num_hidden_layers, attention_mask, layers)
+    seq = bert_encoder(emb, sd, "bert.encoder", cfg, cfg.num_hidden_layers, attention_mask, layers, dropout)
     pooled = torch.tanh(_linear(seq[:, 0], sd, "bert.pooler.dense"))
     # 6. heads
     t = _ln(F.gelu(_linear(seq, sd, "cls.predictions.transform.dense")), sd, "cls.predictions.transform.LayerNorm",
@@ -189,26 +238,29 @@ def forward(sd: Dict[str, Tensor], cfg: OracleConfig, kg_table: Tensor, input_id
     return out
 
 
-def encode(sd, cfg: OracleConfig, kg_table: Tensor, input_ids, attention_mask=None, token_type_ids=None):
+def encode(sd, cfg: OracleConfig, kg_table: Tensor, input_ids, attention_mask=None, token_type_ids=None, dropout=None):
     """Shared front of both models: steps 1-4 of `forward` (sequence_output, pooled_output)."""
     half = cfg.half_length
-    token_embeddings = lm_backbone_forward(sd, cfg, input_ids[:, :half])
+    token_embeddings = lm_backbone_forward(sd, cfg, input_ids[:, :half], dropout)
     ent_ids = input_ids[:, half:]
     if ent_ids.numel() and (int(ent_ids.min()) < 0 or int(ent_ids.max()) >= kg_table.shape[0]):
         raise KeyError(int(ent_ids.max()))
-    inputs_embeds = torch.cat([token_embeddings, kg_table[ent_ids]], dim=1).to(torch.float32)
-    emb = bert_embeddings(sd, "bert.embeddings", cfg, inputs_embeds=inputs_embeds, token_type_ids=token_type_ids)
-    seq = bert_encoder(emb, sd, "bert.encoder", cfg, cfg.num_hidden_layers, attention_mask)
+    inputs_embeds = torch.cat([token_embeddings, kg_table[ent_ids]], dim=1).to(_embeds_dtype(token_embeddings))
+    emb = bert_embeddings(sd, "bert.embeddings", cfg, inputs_embeds=inputs_embeds, token_type_ids=token_type_ids,
+                          dropout=dropout)
+    seq = bert_encoder(emb, sd, "bert.encoder", cfg, cfg.num_hidden_layers, attention_mask, dropout=dropout)
     return seq, torch.tanh(_linear(seq[:, 0], sd, "bert.pooler.dense"))
 
 
 def forward_classification(sd, cfg: OracleConfig, kg_table: Tensor, input_ids, attention_mask=None, token_type_ids=None,
-                           labels=None, problem_type: str = "single_label_classification") -> Dict[str, Tensor]:
+                           labels=None, problem_type: str = "single_label_classification",
+                           dropout=None) -> Dict[str, Tensor]:
     """STonKGsForSequenceClassification.forward (ref:src/stonkgs/models/stonkgs_finetuning.py:259-346): same embedding
-    front and encoder, pooled -> dropout (p = 0 here) -> classifier -> the loss of `problem_type` (:328-338):
-    CrossEntropyLoss / MSELoss on logits.view(-1, num_labels) (torch's own broadcasting included) / BCEWithLogitsLoss."""
-    seq, pooled = encode(sd, cfg, kg_table, input_ids, attention_mask, token_type_ids)
-    logits = _linear(pooled, sd, "classifier")
+    front and encoder, pooled -> dropout (`dropout` None: p = 0; else `_drop` at ("classifier", 0)) -> classifier -> the
+    loss of `problem_type` (:328-338): CrossEntropyLoss / MSELoss on logits.view(-1, num_labels) (torch's own broadcasting
+    included) / BCEWithLogitsLoss."""
+    seq, pooled = encode(sd, cfg, kg_table, input_ids, attention_mask, token_type_ids, dropout)
+    logits = _linear(_drop(pooled, dropout, ("classifier", 0)), sd, "classifier")
     out = {"logits": logits, "pooler_output": pooled, "hidden_states": seq}
     if labels is not None:
         nl = logits.shape[-1]
@@ -308,14 +360,15 @@ class AdamState:
 
 def train_step(sd: Dict[str, Tensor], cfg: OracleConfig, kg_table: Tensor, batch: Dict[str, Tensor], state: AdamState,
                base_lr: float = 1e-4, max_steps: int = 200, max_grad_norm: float = 1.0, betas=(0.9, 0.999),
-               eps: float = 1e-8, weight_decay: float = 0.0, return_outputs: bool = False) -> Dict[str, Tensor]:
+               eps: float = 1e-8, weight_decay: float = 0.0, return_outputs: bool = False,
+               dropout=None) -> Dict[str, Tensor]:
     """One Trainer optimizer step (forward, backward, clip, AdamW, schedule); updates `sd` in place.
-    Returns loss terms, the pre-clip global grad norm and the gradients (for parity checks)."""
+    Returns loss terms, the pre-clip global grad norm and the gradients (for parity checks). `dropout`: see `_drop`."""
     names = trainable_names(sd)
     params = {k: sd[k].detach().clone().requires_grad_(True) for k in names}
     work = dict(sd)
     work.update(params)
-    out = forward(work, cfg, kg_table, **batch)
+    out = forward(work, cfg, kg_table, **batch, dropout=dropout)
     grads = torch.autograd.grad(out["loss"], [params[k] for k in names], allow_unused=True)
     grads = {k: (g if g is not None else torch.zeros_like(sd[k])) for k, g in zip(names, grads)}
     total_norm = torch.sqrt(sum((g.double() ** 2).sum() for g in grads.values())).float()

@@ -175,7 +175,8 @@ def test_out_of_table_entity_raises_keyerror(g2):
 
 def test_dropout_training_mode_is_statistically_consistent(hip):
     """p = 0.1 (the reference's training mode, incl. dropout inside the frozen backbone, quirk Q6): loss stays near the
-    p = 0 loss, differs between steps, and gradients stay finite."""
+    p = 0 loss, differs between steps, and gradients stay finite. (Statistics only: the p = 0.1 step is held to the oracle
+    element by element, under the step's exact masks, in tests/test_step_dropout_gpu.py.)"""
     cfg, sd, tsv_rows, batch, gold, meta = load_case("g2_hipsmall")
     model = _build(cfg, sd, tsv_rows, dropout=0.1)
     model.train()
