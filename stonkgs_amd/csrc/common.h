@@ -30,12 +30,23 @@ static inline int stonk_launch_status() {
   return e == hipSuccess ? STONK_OK : (int)e;
 }
 
+// Grid of a grid-stride launch: one workgroup per `per_block` work items, at least one, at most `cap`.
+static inline unsigned grid_cap(long work_items, long per_block, long cap) {
+  const long g = (work_items + per_block - 1) / per_block;
+  return (unsigned)(g < cap ? (g > 0 ? g : 1) : cap);
+}
+
 #define WAVE 64
 
 // fp32 -> fp16 with the range clamped (STONK_EPI_OUT_F16: an overflowing logit must not become an infinity)
 __device__ __forceinline__ _Float16 to_f16_sat(float v) { return (_Float16)fminf(fmaxf(v, -65504.f), 65504.f); }
 
 __device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ int wave_sum_i(int v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
@@ -128,3 +139,10 @@ static inline uint32_t stonk_drop_thr32(float p) {
   if (t > 4294967295.0) t = 4294967295.0;
   return (uint32_t)(t + 0.5);
 }
+// what a kernel with inverted dropout takes for (p, seed): the keep threshold, the scale of a kept element, the mixed seed
+struct StonkDrop {
+  uint32_t thr32;
+  float scale;
+  uint32_t seed;
+};
+static inline StonkDrop stonk_drop(float p, uint32_t seed) { return {stonk_drop_thr32(p), 1.f / (1.f - p), stonk_seed_mix(seed)}; }

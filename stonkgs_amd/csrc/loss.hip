@@ -7,7 +7,7 @@
 // loss or to any gradient, so the decoders run on the compacted labelled rows (identical loss and
 // gradients, SURVEY.md section 8d "label-sparse"); the row count lives in device memory - no host sync.
 #include <atomic>
-#include "common.h"
+#include "rowwise.h"
 #include "stonk_flags.h"
 
 namespace {
@@ -98,8 +98,10 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const bf16* __restrict
   }
 }
 
-// dst[rows[i]] = src[i] for i < count (dst rows not named keep their content; the caller zeroes dst first)
-__global__ __launch_bounds__(256) void scatter_rows_kernel(const bf16* __restrict__ src, long ld_src,
+// dst[rows[i]] = bf16(src[i]) for i < count (dst rows not named keep their content; the caller zeroes dst first). SrcT = bf16,
+// or float: the split-K dgrad of the decoders accumulates in fp32.
+template <typename SrcT>
+__global__ __launch_bounds__(256) void scatter_rows_kernel(const SrcT* __restrict__ src, long ld_src,
                                                            const int* __restrict__ rows, const int* __restrict__ count,
                                                            bf16* __restrict__ dst, long ld_dst, int cols) {
   const int cnt = *count;
@@ -108,24 +110,7 @@ __global__ __launch_bounds__(256) void scatter_rows_kernel(const bf16* __restric
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
     const long r = i / nch;
     const int c = (int)(i - r * nch);
-    *(bf16x8*)(dst + (long)rows[r] * ld_dst + c * 8) = *(const bf16x8*)(src + r * ld_src + c * 8);
-  }
-}
-
-// fp32 source variant (split-K dgrad of the decoders accumulates in fp32): dst[rows[i]] = bf16(src[i])
-__global__ __launch_bounds__(256) void scatter_rows_f32_kernel(const float* __restrict__ src, long ld_src,
-                                                               const int* __restrict__ rows,
-                                                               const int* __restrict__ count, bf16* __restrict__ dst,
-                                                               long ld_dst, int cols) {
-  const int cnt = *count;
-  const int nch = cols >> 3;
-  const long total = (long)cnt * nch;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    const long r = i / nch;
-    const int c = (int)(i - r * nch);
-    const f32x4 a = *(const f32x4*)(src + r * ld_src + c * 8), b = *(const f32x4*)(src + r * ld_src + c * 8 + 4);
-    bf16x8 o = {(bf16)a[0], (bf16)a[1], (bf16)a[2], (bf16)a[3], (bf16)b[0], (bf16)b[1], (bf16)b[2], (bf16)b[3]};
-    *(bf16x8*)(dst + (long)rows[r] * ld_dst + c * 8) = o;
+    *(bf16x8*)(dst + (long)rows[r] * ld_dst + c * 8) = load8_bf16(src + r * ld_src + c * 8);
   }
 }
 
@@ -145,22 +130,6 @@ constexpr int XENT_POOL = 16;
 __device__ float g_xent_part[XENT_POOL][STONK_XENT_BLOCKS];
 __device__ unsigned g_xent_ticket[XENT_POOL];
 std::atomic<unsigned> g_xent_next{0};
-
-template <typename LT> struct LogitVec;
-template <> struct LogitVec<float> {
-  static __device__ __forceinline__ void load8(const float* x, float (&v)[8]) {
-    const f32x4 a = *(const f32x4*)x, b = *(const f32x4*)(x + 4);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { v[j] = a[j]; v[4 + j] = b[j]; }
-  }
-};
-template <> struct LogitVec<_Float16> {
-  static __device__ __forceinline__ void load8(const _Float16* x, float (&v)[8]) {
-    const f16x8 a = *(const f16x8*)x;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (float)a[j];
-  }
-};
 
 template <typename LT>
 __global__ __launch_bounds__(256) void softmax_xent_kernel(const LT* __restrict__ logits, long ld, int ncols, int npad,
@@ -186,7 +155,7 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(const LT* __restrict_
       for (int u = 0; u < 4; ++u) {
         const int i = i0 + 256 * u + t;
         if (i < n8) {
-          LogitVec<LT>::load8(x + 8 * i, v[u]);
+          load8(x + 8 * i, v[u]);
         } else {
 #pragma unroll
           for (int j = 0; j < 8; ++j) v[u][j] = -__builtin_inff();
@@ -247,7 +216,7 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(const LT* __restrict_
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           const int i = i0 + 256 * u + t;
-          if (i < f8) LogitVec<LT>::load8(x + 8 * i, v[u]);
+          if (i < f8) load8(x + 8 * i, v[u]);
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -380,58 +349,71 @@ extern "C" int stonk_label_compact(const int64_t* labels, int64_t n, int half, i
   return stonk_launch_status();
 }
 
+// the checks the gather / scatter launchers share; `ld_src_align` = elements of the source per 16 bytes
+static int row_copy_check(const void* src, int64_t ld_src, int ld_src_align, const int* rows, const int* count_dev,
+                          const void* dst, int64_t ld_dst, int cols) {
+  STONK_CHECK_ARG(src && rows && count_dev && dst, STONK_EINVAL);
+  STONK_CHECK_ARG(cols > 0 && cols % 8 == 0 && ld_src % ld_src_align == 0 && ld_dst % 8 == 0, STONK_EALIGN);
+  return STONK_OK;
+}
+
 extern "C" int stonk_gather_rows_bf16(const void* src, int64_t ld_src, const int* rows, const int* count_dev, void* dst,
                                       int64_t ld_dst, int cols, int64_t cap, void* stream) {
-  STONK_CHECK_ARG(src && rows && count_dev && dst, STONK_EINVAL);
-  STONK_CHECK_ARG(cols > 0 && cols % 8 == 0 && ld_src % 8 == 0 && ld_dst % 8 == 0 && cap >= 0, STONK_EALIGN);
+  if (const int e = row_copy_check(src, ld_src, 8, rows, count_dev, dst, ld_dst, cols)) return e;
+  STONK_CHECK_ARG(cap >= 0, STONK_EALIGN);
   if (cap == 0) return STONK_OK;
   hipLaunchKernelGGL(gather_rows_kernel, dim3(1024), dim3(256), 0, (hipStream_t)stream, (const bf16*)src, (long)ld_src,
                      rows, count_dev, (bf16*)dst, (long)ld_dst, cols, (long)cap);
   return stonk_launch_status();
 }
 
+template <typename SrcT>
+static int scatter_launch(const SrcT* src, int64_t ld_src, const int* rows, const int* count_dev, void* dst, int64_t ld_dst,
+                          int cols, void* stream) {
+  if (const int e = row_copy_check(src, ld_src, 16 / (int)sizeof(SrcT), rows, count_dev, dst, ld_dst, cols)) return e;
+  hipLaunchKernelGGL(scatter_rows_kernel<SrcT>, dim3(1024), dim3(256), 0, (hipStream_t)stream, src, (long)ld_src, rows,
+                     count_dev, (bf16*)dst, (long)ld_dst, cols);
+  return stonk_launch_status();
+}
+
 extern "C" int stonk_scatter_rows_bf16(const void* src, int64_t ld_src, const int* rows, const int* count_dev,
                                        void* dst, int64_t ld_dst, int cols, void* stream) {
-  STONK_CHECK_ARG(src && rows && count_dev && dst, STONK_EINVAL);
-  STONK_CHECK_ARG(cols > 0 && cols % 8 == 0 && ld_src % 8 == 0 && ld_dst % 8 == 0, STONK_EALIGN);
-  hipLaunchKernelGGL(scatter_rows_kernel, dim3(1024), dim3(256), 0, (hipStream_t)stream, (const bf16*)src, (long)ld_src,
-                     rows, count_dev, (bf16*)dst, (long)ld_dst, cols);
-  return stonk_launch_status();
+  return scatter_launch((const bf16*)src, ld_src, rows, count_dev, dst, ld_dst, cols, stream);
 }
 
 extern "C" int stonk_scatter_rows_f32_to_bf16(const float* src, int64_t ld_src, const int* rows, const int* count_dev,
                                              void* dst, int64_t ld_dst, int cols, void* stream) {
-  STONK_CHECK_ARG(src && rows && count_dev && dst, STONK_EINVAL);
-  STONK_CHECK_ARG(cols > 0 && cols % 8 == 0 && ld_src % 4 == 0 && ld_dst % 8 == 0, STONK_EALIGN);
-  hipLaunchKernelGGL(scatter_rows_f32_kernel, dim3(1024), dim3(256), 0, (hipStream_t)stream, src, (long)ld_src, rows,
-                     count_dev, (bf16*)dst, (long)ld_dst, cols);
+  return scatter_launch(src, ld_src, rows, count_dev, dst, ld_dst, cols, stream);
+}
+
+// LT = float (rows of ld % 4 == 0 elements) or _Float16 (ld % 8 == 0 and a 16-byte aligned base: its 16-byte pieces)
+template <typename LT>
+static int xent_launch(const LT* logits, int64_t ld, int ncols, int npad, const int* targets, const int* count_dev,
+                       float* loss_sum, void* dlogits, int64_t ld_d, float grad_scale, int cap_rows, int* err_flag,
+                       void* stream) {
+  constexpr bool f16 = sizeof(LT) == 2;
+  STONK_CHECK_ARG(logits && targets && count_dev && loss_sum && err_flag && cap_rows >= 0, STONK_EINVAL);
+  STONK_CHECK_ARG(ncols > 0 && npad >= ncols && npad % 8 == 0 && ld >= npad && ld % (f16 ? 8 : 4) == 0, STONK_ESHAPE);
+  STONK_CHECK_ARG(!dlogits || (ld_d >= npad && ld_d % 8 == 0), STONK_ESHAPE);
+  STONK_CHECK_ARG(!f16 || (uintptr_t)logits % 16 == 0, STONK_EALIGN);
+  hipLaunchKernelGGL(softmax_xent_kernel<LT>, dim3(STONK_XENT_BLOCKS), dim3(256), 0, (hipStream_t)stream, logits, (long)ld,
+                     ncols, npad, targets, count_dev, loss_sum, (bf16*)dlogits, (long)ld_d, grad_scale, err_flag, cap_rows,
+                     (int)(g_xent_next.fetch_add(1) % XENT_POOL));
   return stonk_launch_status();
 }
 
 extern "C" int stonk_softmax_xent_fwd_bwd(const float* logits, int64_t ld, int ncols, int npad, const int* targets,
                                           const int* count_dev, float* loss_sum, void* dlogits, int64_t ld_d,
                                           float grad_scale, int cap_rows, int* err_flag, void* stream) {
-  STONK_CHECK_ARG(logits && targets && count_dev && loss_sum && err_flag && cap_rows >= 0, STONK_EINVAL);
-  STONK_CHECK_ARG(ncols > 0 && npad >= ncols && npad % 8 == 0 && ld >= npad && ld % 4 == 0, STONK_ESHAPE);
-  STONK_CHECK_ARG(!dlogits || (ld_d >= npad && ld_d % 8 == 0), STONK_ESHAPE);
-  hipLaunchKernelGGL(softmax_xent_kernel<float>, dim3(STONK_XENT_BLOCKS), dim3(256), 0, (hipStream_t)stream, logits, (long)ld, ncols,
-                     npad, targets, count_dev, loss_sum, (bf16*)dlogits, (long)ld_d, grad_scale, err_flag, cap_rows,
-                     (int)(g_xent_next.fetch_add(1) % XENT_POOL));
-  return stonk_launch_status();
+  return xent_launch(logits, ld, ncols, npad, targets, count_dev, loss_sum, dlogits, ld_d, grad_scale, cap_rows, err_flag,
+                     stream);
 }
 
 extern "C" int stonk_softmax_xent_f16_fwd_bwd(const void* logits_f16, int64_t ld, int ncols, int npad, const int* targets,
                                               const int* count_dev, float* loss_sum, void* dlogits, int64_t ld_d,
                                               float grad_scale, int cap_rows, int* err_flag, void* stream) {
-  STONK_CHECK_ARG(logits_f16 && targets && count_dev && loss_sum && err_flag && cap_rows >= 0, STONK_EINVAL);
-  STONK_CHECK_ARG(ncols > 0 && npad >= ncols && npad % 8 == 0 && ld >= npad && ld % 8 == 0, STONK_ESHAPE);
-  STONK_CHECK_ARG(!dlogits || (ld_d >= npad && ld_d % 8 == 0), STONK_ESHAPE);
-  STONK_CHECK_ARG((uintptr_t)logits_f16 % 16 == 0, STONK_EALIGN);
-  hipLaunchKernelGGL(softmax_xent_kernel<_Float16>, dim3(STONK_XENT_BLOCKS), dim3(256), 0, (hipStream_t)stream,
-                     (const _Float16*)logits_f16, (long)ld, ncols, npad, targets, count_dev, loss_sum, (bf16*)dlogits,
-                     (long)ld_d, grad_scale, err_flag, cap_rows,
-                     (int)(g_xent_next.fetch_add(1) % XENT_POOL));
-  return stonk_launch_status();
+  return xent_launch((const _Float16*)logits_f16, ld, ncols, npad, targets, count_dev, loss_sum, dlogits, ld_d, grad_scale,
+                     cap_rows, err_flag, stream);
 }
 
 extern "C" int stonk_nsp_xent_fwd_bwd(const float* logits, const int64_t* labels, int B, int C, float* loss_sum_cnt,

@@ -7,87 +7,11 @@
 // BertSelfOutput :289-293, BertOutput :347-351, BertPredictionHeadTransform :476-480; the KG gather +
 // concat + cast of ref:src/stonkgs/models/stonkgs_model.py:182-200 (K2/K3 in SURVEY.md section 2.3).
 #include <cstdlib>
-#include "common.h"
+#include <type_traits>
+#include "rowwise.h"
 #include "stonk_flags.h"
 
 namespace {
-
-template <int CPL>
-struct RowRegs {
-  float v[CPL][8];
-};
-
-template <int CPL>
-__device__ __forceinline__ void zero_row(RowRegs<CPL>& r) {
-#pragma unroll
-  for (int i = 0; i < CPL; ++i)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r.v[i][j] = 0.f;
-}
-
-template <int CPL>
-__device__ __forceinline__ void load_bf16_row(const bf16* row, int nch, int lane, RowRegs<CPL>& r) {
-#pragma unroll
-  for (int i = 0; i < CPL; ++i) {
-    const int c = lane + 64 * i;
-    if (c < nch) {
-      const bf16x8 x = *(const bf16x8*)(row + c * 8);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) r.v[i][j] = (float)x[j];
-    } else {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) r.v[i][j] = 0.f;
-    }
-  }
-}
-template <int CPL>
-__device__ __forceinline__ void load_f32_row(const float* row, int nch, int lane, RowRegs<CPL>& r) {
-#pragma unroll
-  for (int i = 0; i < CPL; ++i) {
-    const int c = lane + 64 * i;
-    if (c < nch) {
-      const f32x4 a = *(const f32x4*)(row + c * 8);
-      const f32x4 b = *(const f32x4*)(row + c * 8 + 4);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        r.v[i][j] = a[j];
-        r.v[i][4 + j] = b[j];
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) r.v[i][j] = 0.f;
-    }
-  }
-}
-template <int CPL>
-__device__ __forceinline__ void add_f32_row(const float* row, int nch, int lane, RowRegs<CPL>& r) {
-#pragma unroll
-  for (int i = 0; i < CPL; ++i) {
-    const int c = lane + 64 * i;
-    if (c < nch) {
-      const f32x4 a = *(const f32x4*)(row + c * 8);
-      const f32x4 b = *(const f32x4*)(row + c * 8 + 4);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        r.v[i][j] += a[j];
-        r.v[i][4 + j] += b[j];
-      }
-    }
-  }
-}
-template <int CPL>
-__device__ __forceinline__ void store_bf16_row(bf16* row, int nch, int lane, const RowRegs<CPL>& r) {
-#pragma unroll
-  for (int i = 0; i < CPL; ++i) {
-    const int c = lane + 64 * i;
-    if (c < nch) {
-      bf16x8 o;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) o[j] = (bf16)r.v[i][j];
-      *(bf16x8*)(row + c * 8) = o;
-    }
-  }
-}
 
 // two-pass (mean, then centred variance) statistics in fp32, as torch's native_layer_norm computes them
 template <int CPL>
@@ -150,7 +74,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const bf16* __restri
   const int nch = H >> 3;
   for (long row = (long)blockIdx.x * 4 + wave; row < rows; row += (long)gridDim.x * 4) {
     RowRegs<CPL> r;
-    load_bf16_row<CPL>(x + row * H, nch, lane, r);
+    load_row(x + row * H, nch, lane, r);
     float mean, rstd;
     row_stats<CPL>(r, nch, lane, H, eps, mean, rstd);
     if (lane == 0 && mean_out) {
@@ -286,25 +210,9 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(
 // 200 MB it moves would take 25-40 us): a quarter of its lanes idle on the second 8-element chunk (96 chunks over 64
 // lanes), the dropout switches are run-time branches per element, both row sums go through ds_bpermute, and column keys
 // and gamma are re-derived per row. Here every lane owns EPL columns for the whole launch (one 16-byte piece per 512
-// columns plus an 8-byte piece when EPL % 8 == 4), so gamma and the dropout column keys live in registers, the switches are
-// template parameters, and the two row sums use DPP adds + v_readlane (wave-uniform results in SGPRs).
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float wave_sum_uniform(float v) {   // all 64 lanes must be active
-  v += dpp_mov<0xB1>(v);    // quad_perm [1,0,3,2]
-  v += dpp_mov<0x4E>(v);    // quad_perm [2,3,0,1]
-  v += dpp_mov<0x141>(v);   // row_half_mirror
-  v += dpp_mov<0x140>(v);   // row_mirror: every lane of a 16-lane row now holds the row's sum
-  const int b = __builtin_bit_cast(int, v);
-  const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 0));
-  const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 16));
-  const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 32));
-  const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 48));
-  return (r0 + r1) + (r2 + r3);
-}
-
+// columns plus an 8-byte piece when EPL % 8 == 4: LaneRow in rowwise.h), so gamma and the dropout column keys live in
+// registers, the switches are template parameters, and the two row sums use DPP adds + v_readlane (wave-uniform results in
+// SGPRs: wave_sum_uniform).
 template <int EPL, bool DROP_IN, bool DROP_OUT>
 __global__ __launch_bounds__(256) void layernorm_bwd_lane_kernel(
     const bf16* __restrict__ dy, const bf16* __restrict__ x, const float* __restrict__ mean_in,
@@ -312,12 +220,12 @@ __global__ __launch_bounds__(256) void layernorm_bwd_lane_kernel(
     bf16* __restrict__ dx_drop, float* __restrict__ dgamma, float* __restrict__ dbeta, long rows, uint32_t thr32_in,
     float dscale_in, uint32_t seed_in, uint32_t thr32_out, float dscale_out, uint32_t seed_out, float* __restrict__ ws) {
   extern __shared__ __attribute__((aligned(16))) float sred[];
-  constexpr int H = EPL * 64, NQ = EPL / 8;
-  constexpr bool TAIL = (EPL & 4) != 0;
-  static_assert(EPL % 4 == 0 && EPL >= 4, "lane layout: 4-element granules");
+  typedef LaneRow<EPL> Row;
+  constexpr int H = Row::H, NQ = Row::NQ;
+  constexpr bool TAIL = Row::TAIL;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  auto col_of = [&](int e) { return e < NQ * 8 ? (e >> 3) * 512 + lane * 8 + (e & 7) : NQ * 512 + lane * 4 + (e & 3); };
+  const auto col_of = Row::col_of(lane);
 
   float gam[EPL], ag[EPL], ab[EPL];
   uint32_t ck[EPL];
@@ -330,7 +238,9 @@ __global__ __launch_bounds__(256) void layernorm_bwd_lane_kernel(
 
   const long stride = (long)gridDim.x * 4;
   long row = (long)blockIdx.x * 4 + wave;
-  bf16x8 nx8[NQ > 0 ? NQ : 1], nd8[NQ > 0 ? NQ : 1];
+  // (loads, unpack and stores in this kernel's own text: LaneRow's load_piece / at / store change this row loop's schedule -
+  // profiles/refactor_rowwise_sources.md, item 1)
+  bf16x8 nx8[Row::NQ8], nd8[Row::NQ8];
   bf16x4 nx4, nd4;
   float nmean = 0.f, nrstd = 0.f;
   auto fetch = [&](long r) {
@@ -441,11 +351,11 @@ __global__ __launch_bounds__(256) void layernorm_fwd_lane_kernel(const bf16* __r
                                                                  float* __restrict__ mean_out, float* __restrict__ rstd_out,
                                                                  long rows, float eps, uint32_t thr32, float dscale,
                                                                  uint32_t seed) {
-  constexpr int H = EPL * 64, NQ = EPL / 8;
-  constexpr bool TAIL = (EPL & 4) != 0;
+  typedef LaneRow<EPL> Row;
+  constexpr int H = Row::H;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  auto col_of = [&](int e) { return e < NQ * 8 ? (e >> 3) * 512 + lane * 8 + (e & 7) : NQ * 512 + lane * 4 + (e & 3); };
+  const auto col_of = Row::col_of(lane);
   float gam[EPL], bet[EPL];
   uint32_t ck[EPL];
 #pragma unroll
@@ -456,19 +366,17 @@ __global__ __launch_bounds__(256) void layernorm_fwd_lane_kernel(const bf16* __r
   }
   const long stride = (long)gridDim.x * 4;
   long row = (long)blockIdx.x * 4 + wave;
-  bf16x8 nx8[NQ > 0 ? NQ : 1];
+  bf16x8 nx8[Row::NQ8];
   bf16x4 nx4;
   auto fetch = [&](long r) {
-    const bf16* xr = x + r * H;
 #pragma unroll
-    for (int q = 0; q < NQ; ++q) nx8[q] = *(const bf16x8*)(xr + q * 512 + lane * 8);
-    if (TAIL) nx4 = *(const bf16x4*)(xr + NQ * 512 + lane * 4);
+    for (int q = 0; q < Row::NQ + Row::TAIL; ++q) Row::load_piece(x + r * H, lane, q, nx8, nx4);
   };
   if (row < rows) fetch(row);
   for (; row < rows; row += stride) {
     float v[EPL];
 #pragma unroll
-    for (int e = 0; e < EPL; ++e) v[e] = e < NQ * 8 ? (float)nx8[e >> 3][e & 7] : (float)nx4[e & 3];
+    for (int e = 0; e < EPL; ++e) v[e] = Row::at(nx8, nx4, e);
     if (row + stride < rows) fetch(row + stride);
     float s = 0.f;
 #pragma unroll
@@ -492,20 +400,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_lane_kernel(const bf16* __r
       if (DROP) o = stonk_keep_key(rk, ck[e], thr32) ? o * dscale : 0.f;
       v[e] = o;
     }
-    bf16* yr = y + row * H;
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-      bf16x8 o;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) o[j] = (bf16)v[q * 8 + j];
-      *(bf16x8*)(yr + q * 512 + lane * 8) = o;
-    }
-    if (TAIL) {
-      bf16x4 o;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) o[j] = (bf16)v[NQ * 8 + j];
-      *(bf16x4*)(yr + NQ * 512 + lane * 4) = o;
-    }
+    Row::store(y + row * H, lane, v);
   }
 }
 
@@ -552,8 +447,7 @@ __global__ __launch_bounds__(256) void joint_embed_ln_kernel(
     // zero gradient coming back
     const long pos = pos_of_row ? pos_of_row[row] : row;
     if (pos < 0) {
-      RowRegs<CPL> z;
-      zero_row<CPL>(z);
+      const RowRegs<CPL> z = {};
       if (sum_out) store_bf16_row<CPL>(sum_out + row * H, nch, lane, z);
       store_bf16_row<CPL>(y + row * H, nch, lane, z);
       if (lane == 0 && mean_out) {
@@ -565,22 +459,22 @@ __global__ __launch_bounds__(256) void joint_embed_ln_kernel(
     const int b = (int)(pos / S), s = (int)(pos - (long)b * S);
     RowRegs<CPL> r;
     if (s < half) {
-      load_bf16_row<CPL>(text_hidden + ((long)b * half + s) * H, nch, lane, r);
+      load_row(text_hidden + ((long)b * half + s) * H, nch, lane, r);
     } else {
       long id = input_ids[pos];
       if (id < 0 || id >= kg_rows) {  // the reference raises KeyError here (stonkgs_model.py:185)
         if (lane == 0) atomicOr(err, 1);
         id = 0;
       }
-      load_f32_row<CPL>(kg_table + id * H, nch, lane, r);
+      load_row(kg_table + id * H, nch, lane, r);
     }
     long tt = token_type_ids ? token_type_ids[pos] : 0;
     if (tt < 0 || tt >= type_rows) {
       if (lane == 0) atomicOr(err, 2);
       tt = 0;
     }
-    add_f32_row<CPL>(pos_emb + (long)s * H, nch, lane, r);
-    add_f32_row<CPL>(type_emb + tt * H, nch, lane, r);
+    load_row<true>(pos_emb + (long)s * H, nch, lane, r);
+    load_row<true>(type_emb + tt * H, nch, lane, r);
     if (sum_out) store_bf16_row<CPL>(sum_out + row * H, nch, lane, r);
     float mean, rstd;
     row_stats<CPL>(r, nch, lane, H, eps, mean, rstd);
@@ -615,9 +509,9 @@ __global__ __launch_bounds__(256) void text_embed_ln_kernel(const long* __restri
       id = 0;
     }
     RowRegs<CPL> r;
-    load_f32_row<CPL>(word_emb + id * H, nch, lane, r);
-    add_f32_row<CPL>(pos_emb + (long)s * H, nch, lane, r);
-    add_f32_row<CPL>(type_emb, nch, lane, r);
+    load_row(word_emb + id * H, nch, lane, r);
+    load_row<true>(pos_emb + (long)s * H, nch, lane, r);
+    load_row<true>(type_emb, nch, lane, r);
     float mean, rstd;
     row_stats<CPL>(r, nch, lane, H, eps, mean, rstd);
     normalize_store<CPL>(r, nch, lane, mean, rstd, gamma, beta, y + row * H, row, H, flags & STONK_LN_DROPOUT, thr32,
@@ -687,48 +581,67 @@ __global__ __launch_bounds__(1024) void embed_grad_kernel(const bf16* __restrict
   }
 }
 
-inline int ln_grid(long rows) {
-  long g = (rows + 3) / 4;
-  return (int)(g < 2048 ? (g > 0 ? g : 1) : 2048);
+// ---- host side ------------------------------------------------------------------------------------------------------------
+inline bool ln_shape_ok(int H) { return H > 0 && H % 8 == 0 && H <= 4096; }
+
+// grids of the kernels whose workgroup takes four rows at a time: the generic forward and the embedding front-ends; the
+// lane-layout kernels (fewer, longer-lived workgroups keep gamma and the column keys in registers)
+inline unsigned ln_grid(long rows) { return grid_cap(rows, 4, 2048); }
+inline unsigned ln_lane_grid(long rows) { return grid_cap(rows, 4, 1024); }
+// The grid stonk_layernorm_bwd launches for `rows`, lane or generic: the dgamma / dbeta workspace holds one partial row per
+// workgroup of it, so the workspace query and the deferred reduce must see this very number.
+inline unsigned ln_bwd_grid(long rows) { return ln_lane_grid(rows); }
+
+// f(std::integral_constant<int, N>) with the compile-time width for H: CPL = 16-byte chunks per lane of the generic kernels
+// (any H), EPL = elements per lane of the lane-layout kernels (H = 512 / 768 / 1024 only: false, and no call, otherwise)
+template <typename F>
+void ln_with_cpl(int H, F&& f) {
+  if (H <= 1024) f(std::integral_constant<int, 2>{});
+  else if (H <= 2048) f(std::integral_constant<int, 4>{});
+  else f(std::integral_constant<int, 8>{});
+}
+template <typename F>
+bool ln_with_epl(int H, F&& f) {
+  if (H == 768) f(std::integral_constant<int, 12>{});
+  else if (H == 1024) f(std::integral_constant<int, 16>{});
+  else if (H == 512) f(std::integral_constant<int, 8>{});
+  else return false;
+  return true;
+}
+template <typename F>
+void with_bool(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
+}
+
+void ln_launch_partial_reduce(const float* ws, int nb, int H, float* dgamma, float* dbeta, hipStream_t st) {
+  hipLaunchKernelGGL(ln_partial_reduce_kernel, dim3((2 * H + 255) / 256, 32), dim3(256), 0, st, ws, nb, H, dgamma, dbeta);
 }
 
 }  // namespace
-
-#define LN_DISPATCH(H, CALL)                     \
-  if ((H) <= 1024) { constexpr int CPL = 2; CALL; } \
-  else if ((H) <= 2048) { constexpr int CPL = 4; CALL; } \
-  else { constexpr int CPL = 8; CALL; }
 
 extern "C" int stonk_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean,
                                    float* rstd, int64_t rows, int H, float eps, int flags, float drop_p,
                                    uint32_t seed, void* stream) {
   STONK_CHECK_ARG(x && gamma && beta && y, STONK_EINVAL);
-  STONK_CHECK_ARG(rows >= 0 && H > 0 && H % 8 == 0 && H <= 4096, STONK_ESHAPE);
+  STONK_CHECK_ARG(rows >= 0 && ln_shape_ok(H), STONK_ESHAPE);
   STONK_CHECK_ARG((mean == nullptr) == (rstd == nullptr), STONK_EINVAL);
   if (rows == 0) return STONK_OK;
-  const uint32_t thr = stonk_drop_thr32(drop_p);
-  const float ds = 1.f / (1.f - drop_p);
-  const bool generic_only = false;   // (the lane-owned-column kernels serve H = 512 / 768 / 1024; other widths take the generic ones)
-  const bool drop = (flags & STONK_LN_DROPOUT) != 0;
-#define LN_FWD_LANE(EPL)                                                                                                \
-  do {                                                                                                                  \
-    const int grid = ln_grid(rows) < 1024 ? ln_grid(rows) : 1024;                                                       \
-    if (drop)                                                                                                           \
-      hipLaunchKernelGGL((layernorm_fwd_lane_kernel<EPL, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream,         \
-                         (const bf16*)x, gamma, beta, (bf16*)y, mean, rstd, (long)rows, eps, thr, ds,                   \
-                         stonk_seed_mix(seed));                                                                         \
-    else                                                                                                                \
-      hipLaunchKernelGGL((layernorm_fwd_lane_kernel<EPL, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream,        \
-                         (const bf16*)x, gamma, beta, (bf16*)y, mean, rstd, (long)rows, eps, thr, ds,                   \
-                         stonk_seed_mix(seed));                                                                         \
-  } while (0)
-  if (H == 768 && !generic_only) LN_FWD_LANE(12);
-  else if (H == 1024 && !generic_only) LN_FWD_LANE(16);
-  else if (H == 512 && !generic_only) LN_FWD_LANE(8);
-  else
-  LN_DISPATCH(H, hipLaunchKernelGGL((layernorm_fwd_kernel<CPL>), dim3(ln_grid(rows)), dim3(256), 0,
-                                    (hipStream_t)stream, (const bf16*)x, gamma, beta, (bf16*)y, mean, rstd, (long)rows,
-                                    H, eps, flags, thr, ds, stonk_seed_mix(seed)));
+  const StonkDrop d = stonk_drop(drop_p, seed);
+  const hipStream_t st = (hipStream_t)stream;
+  // (the lane-owned-column kernels serve H = 512 / 768 / 1024; other widths take the generic ones)
+  const bool lane = ln_with_epl(H, [&](auto epl) {
+    with_bool((flags & STONK_LN_DROPOUT) != 0, [&](auto drop) {
+      hipLaunchKernelGGL((layernorm_fwd_lane_kernel<decltype(epl)::value, decltype(drop)::value>), dim3(ln_lane_grid(rows)),
+                         dim3(256), 0, st, (const bf16*)x, gamma, beta, (bf16*)y, mean, rstd, (long)rows, eps, d.thr32,
+                         d.scale, d.seed);
+    });
+  });
+  if (!lane)
+    ln_with_cpl(H, [&](auto cpl) {
+      hipLaunchKernelGGL((layernorm_fwd_kernel<decltype(cpl)::value>), dim3(ln_grid(rows)), dim3(256), 0, st, (const bf16*)x,
+                         gamma, beta, (bf16*)y, mean, rstd, (long)rows, H, eps, flags, d.thr32, d.scale, d.seed);
+    });
   return stonk_launch_status();
 }
 
@@ -736,8 +649,7 @@ extern "C" int stonk_layernorm_fwd(const void* x, const float* gamma, const floa
 // dgamma / dbeta through per-workgroup partials instead of contended atomics.
 extern "C" int64_t stonk_layernorm_bwd_workspace_floats(int64_t rows, int H) {
   if (rows <= 0 || H <= 0) return 0;
-  const int grid = ln_grid(rows) < 1024 ? ln_grid(rows) : 1024;
-  return (int64_t)grid * 2 * H;
+  return (int64_t)ln_bwd_grid(rows) * 2 * H;
 }
 
 extern "C" int stonk_layernorm_bwd(const void* dy, const void* x, const float* mean, const float* rstd,
@@ -746,53 +658,46 @@ extern "C" int stonk_layernorm_bwd(const void* dy, const void* x, const float* m
                                    float drop_p_out, uint32_t seed_out, float* partial_ws, int64_t ws_floats,
                                    void* stream) {
   STONK_CHECK_ARG(dy && x && mean && rstd && gamma && dx, STONK_EINVAL);
-  STONK_CHECK_ARG(rows >= 0 && H > 0 && H % 8 == 0 && H <= 4096, STONK_ESHAPE);
+  STONK_CHECK_ARG(rows >= 0 && ln_shape_ok(H), STONK_ESHAPE);
   STONK_CHECK_ARG((dgamma == nullptr) == (dbeta == nullptr), STONK_EINVAL);
   if (rows == 0) return STONK_OK;
   const size_t lds = dgamma ? (size_t)8 * H * sizeof(float) : 0;
-  const int grid = ln_grid(rows) < 1024 ? ln_grid(rows) : 1024;
+  const int grid = (int)ln_bwd_grid(rows);
   // workspace (grid x 2H floats) given: partial sums + a reduce kernel instead of contended atomics
   float* ws = (dgamma && partial_ws && ws_floats >= (int64_t)grid * 2 * H) ? partial_ws : nullptr;
   if (flags & STONK_LN_DEFER_REDUCE) STONK_CHECK_ARG(ws != nullptr, STONK_EINVAL);   // (needs the workspace)
-  const bool din = (flags & STONK_LN_DROPOUT) != 0, dout = dx_drop != nullptr;
-#define LN_BWD_LANE(EPL, DI, DO)                                                                                       \
-  hipLaunchKernelGGL((layernorm_bwd_lane_kernel<EPL, DI, DO>), dim3(grid), dim3(256), lds, (hipStream_t)stream,         \
-                     (const bf16*)dy, (const bf16*)x, mean, rstd, gamma, (bf16*)dx, (bf16*)dx_drop, dgamma, dbeta,      \
-                     (long)rows, stonk_drop_thr32(drop_p_in), 1.f / (1.f - drop_p_in), stonk_seed_mix(seed_in),         \
-                     stonk_drop_thr32(drop_p_out), 1.f / (1.f - drop_p_out), stonk_seed_mix(seed_out), ws)
-#define LN_BWD_LANE_H(EPL)                                  \
-  do {                                                      \
-    if (din && dout) LN_BWD_LANE(EPL, true, true);          \
-    else if (din) LN_BWD_LANE(EPL, true, false);            \
-    else if (dout) LN_BWD_LANE(EPL, false, true);           \
-    else LN_BWD_LANE(EPL, false, false);                    \
-  } while (0)
-  const bool generic_only = false;
-  if (H == 768 && !generic_only) LN_BWD_LANE_H(12);
-  else if (H == 1024 && !generic_only) LN_BWD_LANE_H(16);
-  else if (H == 512 && !generic_only) LN_BWD_LANE_H(8);
-  else
-  LN_DISPATCH(H, hipLaunchKernelGGL((layernorm_bwd_kernel<CPL>), dim3(grid), dim3(256), lds, (hipStream_t)stream,
-                                    (const bf16*)dy, (const bf16*)x, mean, rstd, gamma, (bf16*)dx, (bf16*)dx_drop,
-                                    dgamma, dbeta, (long)rows, H, flags, stonk_drop_thr32(drop_p_in),
-                                    1.f / (1.f - drop_p_in), stonk_seed_mix(seed_in), stonk_drop_thr32(drop_p_out),
-                                    1.f / (1.f - drop_p_out), stonk_seed_mix(seed_out), ws));
+  const StonkDrop di = stonk_drop(drop_p_in, seed_in), dout = stonk_drop(drop_p_out, seed_out);
+  const hipStream_t st = (hipStream_t)stream;
+  const bool lane = ln_with_epl(H, [&](auto epl) {
+    with_bool((flags & STONK_LN_DROPOUT) != 0, [&](auto drop_in) {
+      with_bool(dx_drop != nullptr, [&](auto drop_out) {
+        constexpr int EPL = decltype(epl)::value;
+        constexpr bool IN = decltype(drop_in)::value, OUT = decltype(drop_out)::value;
+        hipLaunchKernelGGL((layernorm_bwd_lane_kernel<EPL, IN, OUT>),
+                           dim3(grid), dim3(256), lds, st, (const bf16*)dy, (const bf16*)x, mean, rstd, gamma, (bf16*)dx,
+                           (bf16*)dx_drop, dgamma, dbeta, (long)rows, di.thr32, di.scale, di.seed, dout.thr32, dout.scale,
+                           dout.seed, ws);
+      });
+    });
+  });
+  if (!lane)
+    ln_with_cpl(H, [&](auto cpl) {
+      hipLaunchKernelGGL((layernorm_bwd_kernel<decltype(cpl)::value>), dim3(grid), dim3(256), lds, st, (const bf16*)dy,
+                         (const bf16*)x, mean, rstd, gamma, (bf16*)dx, (bf16*)dx_drop, dgamma, dbeta, (long)rows, H, flags,
+                         di.thr32, di.scale, di.seed, dout.thr32, dout.scale, dout.seed, ws);
+    });
   // STONK_LN_DEFER_REDUCE: the partial sums stay in the workspace; the caller finishes with stonk_layernorm_bwd_reduce
   // (the training step puts that launch on its weight-gradient stream: nothing on the main chain waits for dgamma / dbeta)
-  if (ws && !(flags & STONK_LN_DEFER_REDUCE))
-    hipLaunchKernelGGL(ln_partial_reduce_kernel, dim3((2 * H + 255) / 256, 32), dim3(256), 0, (hipStream_t)stream, ws, grid,
-                       H, dgamma, dbeta);
+  if (ws && !(flags & STONK_LN_DEFER_REDUCE)) ln_launch_partial_reduce(ws, grid, H, dgamma, dbeta, st);
   return stonk_launch_status();
 }
 
 extern "C" int stonk_layernorm_bwd_reduce(const float* partial_ws, int64_t rows, int H, float* dgamma, float* dbeta,
                                           void* stream) {
   STONK_CHECK_ARG(partial_ws && dgamma && dbeta, STONK_EINVAL);
-  STONK_CHECK_ARG(rows >= 0 && H > 0 && H % 8 == 0 && H <= 4096, STONK_ESHAPE);
+  STONK_CHECK_ARG(rows >= 0 && ln_shape_ok(H), STONK_ESHAPE);
   if (rows == 0) return STONK_OK;
-  const int grid = ln_grid(rows) < 1024 ? ln_grid(rows) : 1024;   // (as stonk_layernorm_bwd launched for these rows)
-  hipLaunchKernelGGL(ln_partial_reduce_kernel, dim3((2 * H + 255) / 256, 32), dim3(256), 0, (hipStream_t)stream, partial_ws,
-                     grid, H, dgamma, dbeta);
+  ln_launch_partial_reduce(partial_ws, (int)ln_bwd_grid(rows), H, dgamma, dbeta, (hipStream_t)stream);
   return stonk_launch_status();
 }
 
@@ -805,18 +710,19 @@ extern "C" int stonk_joint_embed_ln_fwd(const int64_t* input_ids, const int64_t*
                                         void* stream) {
   STONK_CHECK_ARG(input_ids && text_hidden && kg_table && pos_emb && type_emb && gamma && beta && y && err_flag,
                   STONK_EINVAL);
-  STONK_CHECK_ARG(B >= 0 && S > 0 && half >= 0 && half <= S && H > 0 && H % 8 == 0 && H <= 4096, STONK_ESHAPE);
+  STONK_CHECK_ARG(B >= 0 && S > 0 && half >= 0 && half <= S && ln_shape_ok(H), STONK_ESHAPE);
   STONK_CHECK_ARG(kg_rows > 0 && type_rows > 0, STONK_ESHAPE);
   STONK_CHECK_ARG(!pos_of_row || (n_rows >= 0 && n_rows <= (long)B * S), STONK_ESHAPE);
   if (B == 0) return STONK_OK;
   const long rows = pos_of_row ? (long)n_rows : (long)B * S;
   if (rows == 0) return STONK_OK;
-  LN_DISPATCH(H, hipLaunchKernelGGL((joint_embed_ln_kernel<CPL>), dim3(ln_grid(rows)), dim3(256), 0,
-                                    (hipStream_t)stream, (const long*)input_ids, (const long*)token_type_ids,
-                                    (const bf16*)text_hidden, kg_table, pos_emb, type_emb, gamma, beta,
-                                    (bf16*)sum_out, (bf16*)y, mean, rstd, B, S, half, H, (long)kg_rows, type_rows, eps,
-                                    flags, stonk_drop_thr32(drop_p), 1.f / (1.f - drop_p), stonk_seed_mix(seed), err_flag,
-                                    pos_of_row, (long)n_rows));
+  const StonkDrop d = stonk_drop(drop_p, seed);
+  ln_with_cpl(H, [&](auto cpl) {
+    hipLaunchKernelGGL((joint_embed_ln_kernel<decltype(cpl)::value>), dim3(ln_grid(rows)), dim3(256), 0, (hipStream_t)stream,
+                       (const long*)input_ids, (const long*)token_type_ids, (const bf16*)text_hidden, kg_table, pos_emb,
+                       type_emb, gamma, beta, (bf16*)sum_out, (bf16*)y, mean, rstd, B, S, half, H, (long)kg_rows, type_rows,
+                       eps, flags, d.thr32, d.scale, d.seed, err_flag, pos_of_row, (long)n_rows);
+  });
   return stonk_launch_status();
 }
 
@@ -825,13 +731,15 @@ extern "C" int stonk_text_embed_ln_fwd(const int64_t* input_ids, int64_t ld_ids,
                                        const float* beta, void* y, int B, int S, int H, int64_t vocab, float eps,
                                        int flags, float drop_p, uint32_t seed, int* err_flag, void* stream) {
   STONK_CHECK_ARG(input_ids && word_emb && pos_emb && type_emb && gamma && beta && y && err_flag, STONK_EINVAL);
-  STONK_CHECK_ARG(B >= 0 && S > 0 && ld_ids >= S && H > 0 && H % 8 == 0 && H <= 4096 && vocab > 0, STONK_ESHAPE);
+  STONK_CHECK_ARG(B >= 0 && S > 0 && ld_ids >= S && ln_shape_ok(H) && vocab > 0, STONK_ESHAPE);
   if (B == 0) return STONK_OK;
   const long rows = (long)B * S;
-  LN_DISPATCH(H, hipLaunchKernelGGL((text_embed_ln_kernel<CPL>), dim3(ln_grid(rows)), dim3(256), 0,
-                                    (hipStream_t)stream, (const long*)input_ids, (long)ld_ids, word_emb, pos_emb,
-                                    type_emb, gamma, beta, (bf16*)y, B, S, H, (long)vocab, eps, flags,
-                                    stonk_drop_thr32(drop_p), 1.f / (1.f - drop_p), stonk_seed_mix(seed), err_flag));
+  const StonkDrop d = stonk_drop(drop_p, seed);
+  ln_with_cpl(H, [&](auto cpl) {
+    hipLaunchKernelGGL((text_embed_ln_kernel<decltype(cpl)::value>), dim3(ln_grid(rows)), dim3(256), 0, (hipStream_t)stream,
+                       (const long*)input_ids, (long)ld_ids, word_emb, pos_emb, type_emb, gamma, beta, (bf16*)y, B, S, H,
+                       (long)vocab, eps, flags, d.thr32, d.scale, d.seed, err_flag);
+  });
   return stonk_launch_status();
 }
 
@@ -839,7 +747,7 @@ extern "C" int stonk_embed_grad(const void* dx, const int64_t* token_type_ids, f
                                 int H, int type_rows, const int* row_of_pos, void* stream) {
   STONK_CHECK_ARG(dx && dpos && dtype, STONK_EINVAL);
   // (the kernel keeps sums for type rows 0 and 1 only: a third row would silently get no gradient)
-  STONK_CHECK_ARG(B >= 0 && S > 0 && H > 0 && H % 8 == 0 && H <= 1024 && type_rows >= 1 && type_rows <= 2, STONK_ESHAPE);
+  STONK_CHECK_ARG(B >= 0 && S > 0 && ln_shape_ok(H) && H <= 1024 && type_rows >= 1 && type_rows <= 2, STONK_ESHAPE);
   STONK_CHECK_ARG((uintptr_t)dx % 16 == 0, STONK_EALIGN);
   if (B == 0) return STONK_OK;
   hipLaunchKernelGGL(embed_grad_kernel, dim3(S), dim3((H >> 3) * EG), 0, (hipStream_t)stream, (const bf16*)dx,

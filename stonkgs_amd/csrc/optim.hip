@@ -144,6 +144,18 @@ __device__ __forceinline__ bool in_spans(const long* __restrict__ spans, int n, 
   }
   return lo != 0 && e < spans[2 * (lo - 1) + 1];
 }
+// the last of the n entries of a table sorted by first(i) whose first(i) <= bid: the entry that owns workgroup `bid` of a
+// launch whose grid is the sum of the entries' workgroup counts (first(0) = 0)
+template <typename B, typename F>
+__device__ __forceinline__ int last_entry_at_or_below(int n, B bid, F first) {
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (first(mid) <= bid) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
 
 // The scalars every AdamW kernel derives once per thread, and the update of one group of four elements: ONE definition,
 // so that the flat kernel, its span form and the tiled kernel produce the same bits from the same inputs.
@@ -247,12 +259,7 @@ __global__ __launch_bounds__(256) void adamw_spans_kernel(float* __restrict__ p,
                                                           float grad_scale, const long* __restrict__ decay_spans,
                                                           int n_spans, const long* __restrict__ keep_grad, int n_keep) {
   const long bid = blockIdx.x;
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {   // last entry whose first_chunk <= bid
-    const int mid = (lo + hi + 1) >> 1;
-    if (spans[3 * mid + 2] <= bid) lo = mid;
-    else hi = mid - 1;
-  }
+  const int lo = last_entry_at_or_below(n, bid, [&](int i) { return spans[3 * i + 2]; });
   const long e = spans[3 * lo] + (bid - spans[3 * lo + 2]) * ADAMW_CHUNK + 4 * threadIdx.x;
   if (e >= spans[3 * lo + 1]) return;
   const AdamwConsts c = adamw_consts(lr, bc1, bc2, gnorm_sq, max_norm, grad_scale);
@@ -293,6 +300,23 @@ __device__ __forceinline__ unsigned short bf16_bits(float f) {
 __device__ __forceinline__ float bits_to_float(unsigned short u) {
   return __uint_as_float(((unsigned)u) << 16);
 }
+// The store half of a 64x64 tile transpose: thread t writes out row c0 + (t >> 2), sixteen source rows (r0 + 16 (t & 3) ...)
+// = 32 contiguous bytes, from the tile in LDS. For the threads whose out row exists: if (c0 + (t >> 2) < cols) at the call
+// (with the test in here the compiler lays the branch out differently).
+__device__ __forceinline__ void store_tile_transposed(const unsigned short (&tile)[TT][TT + 2], bf16* out, long ld_out, long r0,
+                                                      int c0, int t) {
+  const int oc = t >> 2, rb = (t & 3) * 16;
+  u16x8 o0, o1;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    o0[j] = tile[rb + j][oc];
+    o1[j] = tile[rb + 8 + j][oc];
+  }
+  bf16* dst = out + (long)(c0 + oc) * ld_out + r0 + rb;
+  *(u16x8*)dst = o0;
+  *(u16x8*)(dst + 8) = o1;
+}
+
 template <typename SrcT>
 __global__ __launch_bounds__(256) void transpose_kernel(const SrcT* __restrict__ in, long ld_in, bf16* __restrict__ out,
                                                         long ld_out, long rows, int cols, float* __restrict__ colsum,
@@ -338,25 +362,7 @@ __global__ __launch_bounds__(256) void transpose_kernel(const SrcT* __restrict__
       for (int j = 0; j < 8; ++j) tile[rr][cc + j] = vals[j];
     }
     __syncthreads();
-    // store: thread -> (out row = column c0 + (t >> 2), 16 source rows = 32 contiguous bytes)
-    {
-      const int oc = t >> 2;
-      const int rb = (t & 3) * 16;
-      if (c0 + oc < cols) {
-        unsigned short vals[16];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) vals[j] = tile[rb + j][oc];
-        bf16* dst = out + (long)(c0 + oc) * ld_out + r0 + rb;
-        u16x8 o0, o1;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          o0[j] = vals[j];
-          o1[j] = vals[8 + j];
-        }
-        *(u16x8*)dst = o0;
-        *(u16x8*)(dst + 8) = o1;
-      }
-    }
+    if (c0 + (t >> 2) < cols) store_tile_transposed(tile, out, ld_out, r0, c0, t);
     if (colsum && t < TT && c0 + t < cols) {
       float s = 0.f;
 #pragma unroll 8
@@ -380,12 +386,7 @@ struct TransposeDesc {
 __global__ __launch_bounds__(256) void transpose_batched_kernel(const TransposeDesc* __restrict__ desc, int n) {
   __shared__ unsigned short tile[TT][TT + 2];
   const int bid = blockIdx.x;
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {   // last entry whose first_tile <= bid
-    const int mid = (lo + hi + 1) >> 1;
-    if (desc[mid].first_tile <= bid) lo = mid;
-    else hi = mid - 1;
-  }
+  const int lo = last_entry_at_or_below(n, bid, [&](int i) { return desc[i].first_tile; });
   const TransposeDesc d = desc[lo];
   const int tl = bid - d.first_tile;
   const long r0 = (long)(tl / d.col_tiles) * TT;
@@ -401,18 +402,7 @@ __global__ __launch_bounds__(256) void transpose_batched_kernel(const TransposeD
     for (int j = 0; j < 8; ++j) tile[rr][cc + j] = v[j];
   }
   __syncthreads();
-  const int oc = t >> 2, rb = (t & 3) * 16;
-  if (c0 + oc < d.cols) {
-    u16x8 o0, o1;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      o0[j] = tile[rb + j][oc];
-      o1[j] = tile[rb + 8 + j][oc];
-    }
-    bf16* dst = d.out + (long)(c0 + oc) * d.ld_out + r0 + rb;
-    *(u16x8*)dst = o0;
-    *(u16x8*)(dst + 8) = o1;
-  }
+  if (c0 + (t >> 2) < d.cols) store_tile_transposed(tile, d.out, d.ld_out, r0, c0, t);
 }
 
 // AdamW over the 2-D weights that have a W^T copy, one 64x64 tile per workgroup: the update of adamw_kernel (the same
@@ -439,12 +429,7 @@ __global__ __launch_bounds__(256) void adamw_tiled_kernel(float* __restrict__ p,
                                                           const long* __restrict__ keep_grad, int n_keep) {
   __shared__ unsigned short tile[TT][TT + 2];
   const int bid = blockIdx.x;
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {   // last entry whose first_tile <= bid
-    const int mid = (lo + hi + 1) >> 1;
-    if (desc[mid].first_tile <= bid) lo = mid;
-    else hi = mid - 1;
-  }
+  const int lo = last_entry_at_or_below(n, bid, [&](int i) { return desc[i].first_tile; });
   const AdamwTileDesc d = desc[lo];
   const int tl = bid - d.first_tile;
   const long r0 = (long)(tl / d.col_tiles) * TT;
@@ -479,24 +464,25 @@ __global__ __launch_bounds__(256) void adamw_tiled_kernel(float* __restrict__ p,
   }
   if (r0 >= d.rows) return;   // (pad rows past the W^T copy's last tile; uniform over the workgroup)
   __syncthreads();
-  const int oc = t >> 2, rb = (t & 3) * 16;
-  if (c0 + oc < d.cols) {
-    u16x8 o0, o1;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      o0[j] = tile[rb + j][oc];
-      o1[j] = tile[rb + 8 + j][oc];
-    }
-    bf16* dst = d.wt + (long)(c0 + oc) * d.ld_out + r0 + rb;
-    *(u16x8*)dst = o0;
-    *(u16x8*)(dst + 8) = o1;
-  }
+  if (c0 + (t >> 2) < d.cols) store_tile_transposed(tile, d.wt, d.ld_out, r0, c0, t);
 }
 
-inline int ew_grid(long n) {
-  long g = (n / 4 + 255) / 256;
-  if (g < 1) g = 1;
-  return (int)(g < 4096 ? g : 4096);
+// grid of the elementwise kernels: a thread takes four elements at a time; at most 4096 workgroups, or `cap` if that is fewer
+inline unsigned ew_grid(long n, long cap = 4096) { return grid_cap(n / 4, 256, cap < 4096 ? cap : 4096); }
+
+// One launch of transpose_kernel<SrcT> after the checks the two entry points share. With `rows_dev` the live row count is
+// unknown on the host: the grid is bounded at 64 row tiles and the workgroups stride.
+template <typename SrcT>
+int transpose_launch(const SrcT* in, int64_t ld_in, void* out, int64_t ld_out, int64_t rows, int cols, float* colsum,
+                     const int* rows_dev, void* stream) {
+  STONK_CHECK_ARG(in && out && rows >= 0 && cols > 0, STONK_EINVAL);
+  STONK_CHECK_ARG(cols % 8 == 0 && ld_in % 8 == 0 && ld_out % 8 == 0, STONK_EALIGN);
+  STONK_CHECK_ARG(ld_out >= ((rows + TT - 1) / TT) * TT, STONK_ESHAPE);
+  if (rows == 0) return STONK_OK;
+  const dim3 grid((cols + TT - 1) / TT, grid_cap(rows, TT, rows_dev ? 64 : 65535));
+  hipLaunchKernelGGL((transpose_kernel<SrcT>), grid, dim3(256), 0, (hipStream_t)stream, in, (long)ld_in, (bf16*)out,
+                     (long)ld_out, (long)rows, cols, colsum, rows_dev);
+  return stonk_launch_status();
 }
 
 }  // namespace
@@ -511,9 +497,8 @@ extern "C" int stonk_sumsq_f32_plus(const float* x, int64_t n, float* out_accum,
   STONK_CHECK_ARG(ws_floats >= SUMSQ_MAX_BLOCKS + 1, STONK_EINVAL);
   STONK_CHECK_ARG((uintptr_t)x % 16 == 0 && (uintptr_t)workspace % 4 == 0 && (uintptr_t)extra % 4 == 0, STONK_EALIGN);
   if (n == 0 && n_extra == 0) return STONK_OK;
-  const int grid = ew_grid(n) < SUMSQ_MAX_BLOCKS ? ew_grid(n) : SUMSQ_MAX_BLOCKS;
-  hipLaunchKernelGGL(sumsq_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, (long)n, out_accum, workspace,
-                     (unsigned*)(workspace + SUMSQ_MAX_BLOCKS), extra, (long)n_extra);
+  hipLaunchKernelGGL(sumsq_kernel, dim3(ew_grid(n, SUMSQ_MAX_BLOCKS)), dim3(256), 0, (hipStream_t)stream, x, (long)n,
+                     out_accum, workspace, (unsigned*)(workspace + SUMSQ_MAX_BLOCKS), extra, (long)n_extra);
   return stonk_launch_status();
 }
 
@@ -531,9 +516,9 @@ extern "C" int stonk_adamw_step(float* p, float* g, float* m, float* v, void* p_
   STONK_CHECK_ARG(((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) % 16 == 0, STONK_EALIGN);
   STONK_CHECK_ARG(bias_corr1 > 0.f && bias_corr2 > 0.f, STONK_EINVAL);
   if (n == 0) return STONK_OK;
-  hipLaunchKernelGGL(adamw_kernel, dim3(ew_grid(n) < STONK_ADAMW_BLOCKS ? ew_grid(n) : STONK_ADAMW_BLOCKS), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16*)p_bf16,
-                     (long)n, lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, gnorm_sq_dev, max_grad_norm,
-                     grad_scale, (const long*)decay_spans, n_spans, (long)span_base, (const long*)nullptr, 0);
+  hipLaunchKernelGGL(adamw_kernel, dim3(ew_grid(n, STONK_ADAMW_BLOCKS)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
+                     (bf16*)p_bf16, (long)n, lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, gnorm_sq_dev,
+                     max_grad_norm, grad_scale, (const long*)decay_spans, n_spans, (long)span_base, (const long*)nullptr, 0);
   return stonk_launch_status();
 }
 
@@ -589,17 +574,7 @@ extern "C" int stonk_cast_f32_to_bf16(const float* x, void* y, int64_t n, void* 
 // out[c][r] = in[r][c] for r < rows (rows >= *rows_dev read as zero), c < cols. out needs ld_out >= roundup(rows, 64).
 extern "C" int stonk_transpose_bf16(const void* in, int64_t ld_in, void* out, int64_t ld_out, int64_t rows, int cols,
                                     float* colsum, const int* rows_dev, void* stream) {
-  STONK_CHECK_ARG(in && out && rows >= 0 && cols > 0, STONK_EINVAL);
-  STONK_CHECK_ARG(cols % 8 == 0 && ld_in % 8 == 0 && ld_out % 8 == 0, STONK_EALIGN);
-  STONK_CHECK_ARG(ld_out >= ((rows + TT - 1) / TT) * TT, STONK_ESHAPE);
-  if (rows == 0) return STONK_OK;
-  long rtiles = (rows + TT - 1) / TT;
-  if (rows_dev && rtiles > 64) rtiles = 64;  // live count unknown on the host: bounded grid, blocks stride
-  if (rtiles > 65535) rtiles = 65535;
-  const dim3 grid((cols + TT - 1) / TT, (unsigned)rtiles);
-  hipLaunchKernelGGL((transpose_kernel<bf16>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)in, (long)ld_in,
-                     (bf16*)out, (long)ld_out, (long)rows, cols, colsum, rows_dev);
-  return stonk_launch_status();
+  return transpose_launch((const bf16*)in, ld_in, out, ld_out, rows, cols, colsum, rows_dev, stream);
 }
 
 extern "C" int stonk_transpose_bf16_batched(const void* desc_dev, int n, int total_tiles, void* stream) {
@@ -613,14 +588,5 @@ extern "C" int stonk_transpose_bf16_batched(const void* desc_dev, int n, int tot
 // bf16 W^T copy of a dense fp32 [rows, cols] master weight: out[c][r] = bf16(in[r][c])
 extern "C" int stonk_transpose_f32_to_bf16(const float* in, void* out, int64_t rows, int cols, int64_t ld_out,
                                            void* stream) {
-  STONK_CHECK_ARG(in && out && rows >= 0 && cols > 0, STONK_EINVAL);
-  STONK_CHECK_ARG(cols % 8 == 0 && ld_out % 8 == 0, STONK_EALIGN);
-  STONK_CHECK_ARG(ld_out >= ((rows + TT - 1) / TT) * TT, STONK_ESHAPE);
-  if (rows == 0) return STONK_OK;
-  long rtiles = (rows + TT - 1) / TT;
-  if (rtiles > 65535) rtiles = 65535;
-  const dim3 grid((cols + TT - 1) / TT, (unsigned)rtiles);
-  hipLaunchKernelGGL((transpose_kernel<float>), grid, dim3(256), 0, (hipStream_t)stream, in, (long)cols, (bf16*)out,
-                     (long)ld_out, (long)rows, cols, (float*)nullptr, (const int*)nullptr);
-  return stonk_launch_status();
+  return transpose_launch(in, cols, out, ld_out, rows, cols, (float*)nullptr, (const int*)nullptr, stream);   // (dense: ld_in = cols)
 }

@@ -10,6 +10,15 @@ namespace {
 __device__ __forceinline__ float load_x(const void* x, long idx, bool f32) {
   return f32 ? ((const float*)x)[idx] : (float)((const bf16*)x)[idx];
 }
+// the gradient in front of the activation: dpre = dy * (1 - y^2) for tanh (th), else dy
+__device__ __forceinline__ float small_dpre(const float* dy, const float* y, long idx, bool th) {
+  float d = dy[idx];
+  if (th) {
+    const float yy = y[idx];
+    d *= 1.f - yy * yy;
+  }
+  return d;
+}
 
 // y[m][n] = act(sum_k x[m*ldx + k] * W[n][k] + bias[n]);  one wave per (m, n)
 __global__ __launch_bounds__(256) void small_linear_fwd_kernel(const void* __restrict__ x, long ldx,
@@ -35,7 +44,6 @@ __global__ __launch_bounds__(256) void small_linear_fwd_kernel(const void* __res
 
 constexpr int WG_MC = 64;   // rows per piece of the weight-gradient sums (both kernels)
 
-// dpre = dy * (1 - y^2) for tanh, else dy.
 // dW[n][k] += sum_m dpre[m][n] x[m][k];  db[n] += sum_m dpre[m][n]     (one thread per (n, k))
 __global__ __launch_bounds__(256) void small_linear_wgrad_kernel(const float* __restrict__ dy, const float* __restrict__ y,
                                                                  const void* __restrict__ x, long ldx,
@@ -51,11 +59,7 @@ __global__ __launch_bounds__(256) void small_linear_wgrad_kernel(const float* __
       const int m1 = m0 + WG_MC < M ? m0 + WG_MC : M;
       float a = 0.f, ab = 0.f;
       for (int m = m0; m < m1; ++m) {
-        float d = dy[(long)m * N + n];
-        if (th) {
-          const float yy = y[(long)m * N + n];
-          d *= 1.f - yy * yy;
-        }
+        const float d = small_dpre(dy, y, (long)m * N + n, th);
         a += d * load_x(x, (long)m * ldx + k, xf32);
         ab += d;
       }
@@ -81,15 +85,7 @@ __global__ __launch_bounds__(256) void small_linear_wgrad_tiled_kernel(const flo
   const int n0 = blockIdx.y * WG_NT, k = blockIdx.x * 256 + threadIdx.x;
   for (int idx = threadIdx.x; idx < M * WG_NT; idx += 256) {
     const int m = idx / WG_NT, n = n0 + idx % WG_NT;
-    float d = 0.f;
-    if (n < N) {
-      d = dy[(long)m * N + n];
-      if (th) {
-        const float yy = y[(long)m * N + n];
-        d *= 1.f - yy * yy;
-      }
-    }
-    dpre_t[idx] = d;
+    dpre_t[idx] = n < N ? small_dpre(dy, y, (long)m * N + n, th) : 0.f;
   }
   __syncthreads();
   if (k < K) {
@@ -135,7 +131,7 @@ __global__ __launch_bounds__(256) void small_linear_dgrad_kernel(const float* __
   extern __shared__ __attribute__((aligned(16))) float dpre[];
   const bool th = act & STONK_SMALL_TANH;
   const int m = blockIdx.y;
-  for (int n = threadIdx.x; n < N; n += 256) {
+  for (int n = threadIdx.x; n < N; n += 256) {   // (small_dpre's text, not a call: through it this loop compiles to other code)
     float d = dy[(long)m * N + n];
     if (th) {
       const float yy = y[(long)m * N + n];
@@ -164,45 +160,8 @@ __global__ __launch_bounds__(256) void small_linear_dgrad_kernel(const float* __
   }
 }
 
-}  // namespace
-
-extern "C" int stonk_small_linear_fwd(const void* x, int64_t ldx, const float* W, const float* bias, float* y, int M,
-                                      int N, int K, int act, void* stream) {
-  STONK_CHECK_ARG(x && W && y, STONK_EINVAL);
-  STONK_CHECK_ARG(M >= 0 && N > 0 && K > 0 && ldx >= K, STONK_ESHAPE);
-  if (M == 0) return STONK_OK;
-  long waves = (long)M * N;
-  int grid = (int)((waves + 3) / 4 < 2048 ? (waves + 3) / 4 : 2048);
-  hipLaunchKernelGGL(small_linear_fwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, (long)ldx, W, bias, y, M,
-                     N, K, act);
-  return stonk_launch_status();
-}
-
-extern "C" int stonk_small_linear_bwd(const float* dy, const float* y, const void* x, int64_t ldx, const float* W,
-                                      float* dW, float* db, float* dx_f32, void* dx_bf16_accum, int64_t ld_dxb, int M,
-                                      int N, int K, int act, void* stream) {
-  STONK_CHECK_ARG(dy && x && W && dW, STONK_EINVAL);
-  STONK_CHECK_ARG(!(act & STONK_SMALL_TANH) || y, STONK_EINVAL);
-  STONK_CHECK_ARG(M >= 0 && N > 0 && K > 0 && ldx >= K, STONK_ESHAPE);
-  if (M == 0) return STONK_OK;
-  hipStream_t st = (hipStream_t)stream;
-  long nk = (long)N * K;
-  if ((size_t)M * WG_NT * sizeof(float) <= 48 * 1024)
-    hipLaunchKernelGGL(small_linear_wgrad_tiled_kernel, dim3((K + 255) / 256, (N + WG_NT - 1) / WG_NT), dim3(256),
-                       (size_t)M * WG_NT * sizeof(float), st, dy, y, x, (long)ldx, dW, db, M, N, K, act);
-  else
-    hipLaunchKernelGGL(small_linear_wgrad_kernel, dim3((unsigned)((nk + 255) / 256 < 4096 ? (nk + 255) / 256 : 4096)),
-                       dim3(256), 0, st, dy, y, x, (long)ldx, dW, db, M, N, K, act);
-  if (dx_f32 || dx_bf16_accum) {
-    hipLaunchKernelGGL(small_linear_dgrad_kernel, dim3((K + 255) / 256, M), dim3(256), (size_t)N * sizeof(float), st, dy,
-                       y, W, dx_f32, (bf16*)dx_bf16_accum, (long)ld_dxb, M, N, K, act);
-  }
-  return stonk_launch_status();
-}
-
 // du = dg * gelu'(u)  (bf16, elementwise): backward of the GELU inside BertPredictionHeadTransform
 // (hf:models/bert/modeling_bert.py:476-480), where no GEMM epilogue is available to carry it.
-namespace {
 __global__ __launch_bounds__(256) void gelu_bwd_kernel(const bf16* __restrict__ dg, const bf16* __restrict__ u,
                                                        bf16* __restrict__ du, long n8) {
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n8; i += (long)gridDim.x * 256) {
@@ -213,21 +172,8 @@ __global__ __launch_bounds__(256) void gelu_bwd_kernel(const bf16* __restrict__ 
     *(bf16x8*)(du + 8 * i) = o;
   }
 }
-}  // namespace
-
-extern "C" int stonk_gelu_bwd_bf16(const void* dg, const void* u, void* du, int64_t n, void* stream) {
-  STONK_CHECK_ARG(dg && u && du && n >= 0 && n % 8 == 0, STONK_EINVAL);
-  if (n == 0) return STONK_OK;
-  const long n8 = n / 8;
-  const long g = (n8 + 255) / 256;
-  hipLaunchKernelGGL(gelu_bwd_kernel, dim3((unsigned)(g < 4096 ? g : 4096)), dim3(256), 0, (hipStream_t)stream,
-                     (const bf16*)dg, (const bf16*)u, (bf16*)du, n8);
-  return stonk_launch_status();
-}
-
 // Inverted dropout on a small fp32 tensor (the pooled vector in front of the classification head,
 // ref:src/stonkgs/models/stonkgs_finetuning.py:313); the same call with the same (seed) replays the mask on the gradient.
-namespace {
 __global__ __launch_bounds__(256) void dropout_f32_kernel(const float* __restrict__ x, float* __restrict__ y, long n,
                                                           uint32_t thr32, float scale, uint32_t seed) {
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256)
@@ -309,6 +255,46 @@ __global__ __launch_bounds__(256) void elementwise_loss_kernel(const float* __re
 
 }  // namespace
 
+extern "C" int stonk_small_linear_fwd(const void* x, int64_t ldx, const float* W, const float* bias, float* y, int M,
+                                      int N, int K, int act, void* stream) {
+  STONK_CHECK_ARG(x && W && y, STONK_EINVAL);
+  STONK_CHECK_ARG(M >= 0 && N > 0 && K > 0 && ldx >= K, STONK_ESHAPE);
+  if (M == 0) return STONK_OK;
+  hipLaunchKernelGGL(small_linear_fwd_kernel, dim3(grid_cap((long)M * N, 4, 2048)), dim3(256), 0, (hipStream_t)stream, x,
+                     (long)ldx, W, bias, y, M, N, K, act);
+  return stonk_launch_status();
+}
+
+extern "C" int stonk_small_linear_bwd(const float* dy, const float* y, const void* x, int64_t ldx, const float* W,
+                                      float* dW, float* db, float* dx_f32, void* dx_bf16_accum, int64_t ld_dxb, int M,
+                                      int N, int K, int act, void* stream) {
+  STONK_CHECK_ARG(dy && x && W && dW, STONK_EINVAL);
+  STONK_CHECK_ARG(!(act & STONK_SMALL_TANH) || y, STONK_EINVAL);
+  STONK_CHECK_ARG(M >= 0 && N > 0 && K > 0 && ldx >= K, STONK_ESHAPE);
+  if (M == 0) return STONK_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if ((size_t)M * WG_NT * sizeof(float) <= 48 * 1024)
+    hipLaunchKernelGGL(small_linear_wgrad_tiled_kernel, dim3((K + 255) / 256, (N + WG_NT - 1) / WG_NT), dim3(256),
+                       (size_t)M * WG_NT * sizeof(float), st, dy, y, x, (long)ldx, dW, db, M, N, K, act);
+  else
+    hipLaunchKernelGGL(small_linear_wgrad_kernel, dim3(grid_cap((long)N * K, 256, 4096)), dim3(256), 0, st, dy, y, x,
+                       (long)ldx, dW, db, M, N, K, act);
+  if (dx_f32 || dx_bf16_accum) {
+    hipLaunchKernelGGL(small_linear_dgrad_kernel, dim3((K + 255) / 256, M), dim3(256), (size_t)N * sizeof(float), st, dy,
+                       y, W, dx_f32, (bf16*)dx_bf16_accum, (long)ld_dxb, M, N, K, act);
+  }
+  return stonk_launch_status();
+}
+
+extern "C" int stonk_gelu_bwd_bf16(const void* dg, const void* u, void* du, int64_t n, void* stream) {
+  STONK_CHECK_ARG(dg && u && du && n >= 0 && n % 8 == 0, STONK_EINVAL);
+  if (n == 0) return STONK_OK;
+  const long n8 = n / 8;
+  hipLaunchKernelGGL(gelu_bwd_kernel, dim3(grid_cap(n8, 256, 4096)), dim3(256), 0, (hipStream_t)stream,
+                     (const bf16*)dg, (const bf16*)u, (bf16*)du, n8);
+  return stonk_launch_status();
+}
+
 extern "C" int stonk_elementwise_loss_fwd_bwd(const float* logits, const float* targets, int B, int C, int mode,
                                               float* loss_out, float* dlogits, float grad_scale, void* stream) {
   STONK_CHECK_ARG(logits && targets && loss_out, STONK_EINVAL);
@@ -323,9 +309,9 @@ extern "C" int stonk_elementwise_loss_fwd_bwd(const float* logits, const float* 
 extern "C" int stonk_dropout_f32(const float* x, float* y, int64_t n, float p, uint32_t seed, void* stream) {
   STONK_CHECK_ARG(x && y && n >= 0 && p >= 0.f && p < 1.f, STONK_EINVAL);
   if (n == 0) return STONK_OK;
-  const long g = (n + 255) / 256;
-  hipLaunchKernelGGL(dropout_f32_kernel, dim3((unsigned)(g < 1024 ? g : 1024)), dim3(256), 0, (hipStream_t)stream, x, y,
-                     (long)n, stonk_drop_thr32(p), 1.f / (1.f - p), stonk_seed_mix(seed));
+  const StonkDrop d = stonk_drop(p, seed);
+  hipLaunchKernelGGL(dropout_f32_kernel, dim3(grid_cap(n, 256, 1024)), dim3(256), 0, (hipStream_t)stream, x, y, (long)n,
+                     d.thr32, d.scale, d.seed);
   return stonk_launch_status();
 }
 

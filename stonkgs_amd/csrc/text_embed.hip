@@ -61,8 +61,7 @@ extern "C" int stonk_word_embed_grad(const void* dsum, int64_t ld, const int64_t
   STONK_CHECK_ARG((uintptr_t)dsum % 16 == 0 && ld % 8 == 0 && (uintptr_t)dword % 4 == 0, STONK_EALIGN);
   if (B == 0) return STONK_OK;
   const long n_pos = (long)B * S;
-  const long blocks = (n_pos + WEG_WAVES - 1) / WEG_WAVES;
-  hipLaunchKernelGGL(word_embed_grad_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(64 * WEG_WAVES), 0,
+  hipLaunchKernelGGL(word_embed_grad_kernel, dim3(grid_cap(n_pos, WEG_WAVES, 8192)), dim3(64 * WEG_WAVES), 0,
                      (hipStream_t)stream, (const bf16*)dsum, (long)ld, (const long*)input_ids, row_of_pos, dword, (long)ld_w,
                      (long)vocab, padding_idx, n_pos, H, err_flag);
   return stonk_launch_status();

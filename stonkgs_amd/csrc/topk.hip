@@ -15,7 +15,7 @@
 // The merge: every wave selects its k best keys by k rounds of a wave-wide maximum (cross-lane shuffles, the owner pops),
 // the four waves' candidates meet in LDS and wave 0 selects the row's k best from them the same way. No atomics, no
 // workspace; the same input gives the same bits.
-#include "common.h"
+#include "rowwise.h"
 
 namespace {
 
@@ -37,28 +37,6 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long x)
   }
   return x;
 }
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-template <typename LT> struct RowVec;
-template <> struct RowVec<float> {
-  static __device__ __forceinline__ void load8(const float* x, float (&v)[8]) {
-    const f32x4 a = *(const f32x4*)x, b = *(const f32x4*)(x + 4);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { v[j] = a[j]; v[4 + j] = b[j]; }
-  }
-};
-template <> struct RowVec<_Float16> {
-  static __device__ __forceinline__ void load8(const _Float16* x, float (&v)[8]) {
-    const f16x8 a = *(const f16x8*)x;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (float)a[j];
-  }
-};
-
 // the lane's sorted list: keys[0] the best; 0 = empty (below every real key). KC >= k slots; the k-th decides what enters.
 template <int KC> struct LaneTop {
   unsigned long long keys[KC];
@@ -130,7 +108,7 @@ __global__ __launch_bounds__(256) void row_topk_kernel(const LT* __restrict__ lo
       for (int u = 0; u < 4; ++u) {
         const int i = i0 + 256 * u + t;
         if (i < n8) {
-          RowVec<LT>::load8(x + 8 * (long)i, v[u]);
+          load8(x + 8 * (long)i, v[u]);
         } else {
 #pragma unroll
           for (int j = 0; j < 8; ++j) v[u][j] = -__builtin_inff();
@@ -240,7 +218,7 @@ int launch_row_topk(const LT* logits, int64_t ld, int ncols, const int* targets,
   // 16-byte pieces need 16-byte aligned rows; anything else is swept element by element (same results)
   constexpr int per16 = 16 / (int)sizeof(LT);
   const int vec = (uintptr_t)logits % 16 == 0 && ld % per16 == 0;
-  const dim3 grid(cap_rows < 2048 ? cap_rows : 2048), block(256);
+  const dim3 grid(grid_cap(cap_rows, 1, 2048)), block(256);
   const hipStream_t st = (hipStream_t)stream;
 #define STONK_TOPK_LAUNCH(KC)                                                                                          \
   hipLaunchKernelGGL((row_topk_kernel<LT, KC>), grid, block, 0, st, logits, (long)ld, ncols, targets, count_dev, cap_rows, \

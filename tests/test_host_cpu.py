@@ -140,6 +140,124 @@ def test_bad_arguments_are_rejected_without_touching_the_gpu():
     assert lib.stonk_comm_reduce_scatter_async(0, 16, 16, 4, 0, 0) == -1 and lib.stonk_comm_allgather_async(0, 16, 16, 4, 7, 0) == -1
     assert lib.stonk_comm_init(None, 1, 0, 0, 0) == -1 and lib.stonk_comm_destroy(0) == -1 and lib.stonk_comm_unique_id(0) == -1
     assert not lib.stonk_comm_stream(0)
+    # The row-wise sources (norm / loss / small / optim / topk / text_embed .hip): every launcher, one refused call per
+    # distinct check with its exact code (-1 argument, -2 shape, -3 alignment) and one empty call that returns 0 before
+    # anything is launched. P = some non-null 16-byte aligned address that is never dereferenced. The order of the checks
+    # is part of the contract: the first failing one decides the code.
+    P, TANH, DEFER = 16, _hip.SMALL_TANH, _hip.LN_DEFER_REDUCE
+    table = [
+        ("stonk_layernorm_fwd", (P, P, P, P, 0, 0, 4, 12, 1e-12, 0, 0.0, 0, 0), -2),           # H % 8
+        ("stonk_layernorm_fwd", (P, P, P, P, 0, 0, 4, 4104, 1e-12, 0, 0.0, 0, 0), -2),         # H > 4096
+        ("stonk_layernorm_fwd", (P, P, P, P, 0, 0, -1, 768, 1e-12, 0, 0.0, 0, 0), -2),
+        ("stonk_layernorm_fwd", (P, P, P, P, P, 0, 4, 768, 1e-12, 0, 0.0, 0, 0), -1),          # mean without rstd
+        ("stonk_layernorm_fwd", (P, P, P, P, P, 0, 4, 12, 1e-12, 0, 0.0, 0, 0), -2),           # (the shape is looked at first)
+        ("stonk_layernorm_fwd", (0, P, P, P, 0, 0, 4, 768, 1e-12, 0, 0.0, 0, 0), -1),
+        ("stonk_layernorm_fwd", (P, P, P, P, 0, 0, 0, 768, 1e-12, 0, 0.1, 0, 0), 0),
+        ("stonk_layernorm_bwd", (0, P, P, P, P, P, 0, 0, 0, 4, 768, 0, 0.0, 0, 0.0, 0, 0, 0, 0), -1),
+        ("stonk_layernorm_bwd", (P, P, P, P, P, P, 0, 0, 0, 4, 12, 0, 0.0, 0, 0.0, 0, 0, 0, 0), -2),
+        ("stonk_layernorm_bwd", (P, P, P, P, P, P, 0, 0, 0, 4, 4104, 0, 0.0, 0, 0.0, 0, 0, 0, 0), -2),
+        ("stonk_layernorm_bwd", (P, P, P, P, P, P, 0, P, 0, 4, 768, 0, 0.0, 0, 0.0, 0, 0, 0, 0), -1),      # dgamma without dbeta
+        ("stonk_layernorm_bwd", (P, P, P, P, P, P, 0, P, P, 4, 768, DEFER, 0.0, 0, 0.0, 0, 0, 0, 0), -1),  # deferred: no workspace
+        ("stonk_layernorm_bwd", (P, P, P, P, P, P, 0, P, P, 4, 768, DEFER, 0.0, 0, 0.0, 0, P, 1535, 0), -1),  # ... a short one
+        ("stonk_layernorm_bwd", (P, P, P, P, P, P, 0, P, P, 0, 768, DEFER, 0.0, 0, 0.0, 0, 0, 0, 0), 0),   # (no rows: ok before that)
+        ("stonk_layernorm_bwd_reduce", (0, 4, 768, P, P, 0), -1),
+        ("stonk_layernorm_bwd_reduce", (P, 4, 12, P, P, 0), -2),
+        ("stonk_layernorm_bwd_reduce", (P, 0, 768, P, P, 0), 0),
+        ("stonk_joint_embed_ln_fwd", (P, 0, P, P, P, P, P, P, 0, P, 0, 0, 2, 8, 4, 768, 9, 2, 1e-12, 0, 0.0, 0, 0, 0, 0, 0), -1),
+        ("stonk_joint_embed_ln_fwd", (P, 0, P, P, P, P, P, P, 0, P, 0, 0, 2, 8, 4, 12, 9, 2, 1e-12, 0, 0.0, 0, P, 0, 0, 0), -2),
+        ("stonk_joint_embed_ln_fwd", (P, 0, P, P, P, P, P, P, 0, P, 0, 0, 2, 8, 9, 768, 9, 2, 1e-12, 0, 0.0, 0, P, 0, 0, 0), -2),
+        ("stonk_joint_embed_ln_fwd", (P, 0, P, P, P, P, P, P, 0, P, 0, 0, 2, 8, 4, 768, 0, 2, 1e-12, 0, 0.0, 0, P, 0, 0, 0), -2),
+        ("stonk_joint_embed_ln_fwd", (P, 0, P, P, P, P, P, P, 0, P, 0, 0, 2, 8, 4, 768, 9, 2, 1e-12, 0, 0.0, 0, P, P, 17, 0), -2),
+        ("stonk_joint_embed_ln_fwd", (P, 0, P, P, P, P, P, P, 0, P, 0, 0, 0, 8, 4, 768, 9, 2, 1e-12, 0, 0.0, 0, P, 0, 0, 0), 0),
+        ("stonk_joint_embed_ln_fwd", (P, 0, P, P, P, P, P, P, 0, P, 0, 0, 2, 8, 4, 768, 9, 2, 1e-12, 0, 0.0, 0, P, P, 0, 0), 0),
+        ("stonk_text_embed_ln_fwd", (P, 8, P, P, P, P, P, 0, 2, 8, 768, 9, 1e-12, 0, 0.0, 0, P, 0), -1),
+        ("stonk_text_embed_ln_fwd", (P, 7, P, P, P, P, P, P, 2, 8, 768, 9, 1e-12, 0, 0.0, 0, P, 0), -2),
+        ("stonk_text_embed_ln_fwd", (P, 8, P, P, P, P, P, P, 2, 8, 4104, 9, 1e-12, 0, 0.0, 0, P, 0), -2),
+        ("stonk_text_embed_ln_fwd", (P, 8, P, P, P, P, P, P, 2, 8, 768, 0, 1e-12, 0, 0.0, 0, P, 0), -2),
+        ("stonk_text_embed_ln_fwd", (P, 8, P, P, P, P, P, P, 0, 8, 768, 9, 1e-12, 0, 0.0, 0, P, 0), 0),
+        ("stonk_embed_grad", (P, 0, 0, P, 2, 8, 768, 2, 0, 0), -1),
+        ("stonk_embed_grad", (P, 0, P, P, 2, 8, 768, 3, 0, 0), -2),      # a third type row would get no gradient
+        ("stonk_embed_grad", (P, 0, P, P, 2, 8, 2048, 2, 0, 0), -2),     # (one workgroup holds a row: H <= 1024)
+        ("stonk_embed_grad", (P, 0, P, P, 2, 8, 12, 2, 0, 0), -2),
+        ("stonk_embed_grad", (8, 0, P, P, 2, 8, 768, 2, 0, 0), -3),
+        ("stonk_embed_grad", (P, 0, P, P, 0, 8, 768, 2, 0, 0), 0),
+        ("stonk_word_embed_grad", (P, 768, P, 0, 0, 768, 9, -1, 2, 8, 768, P, 0), -1),
+        ("stonk_word_embed_grad", (P, 760, P, 0, P, 768, 9, -1, 2, 8, 768, P, 0), -2),
+        ("stonk_word_embed_grad", (P, 772, P, 0, P, 768, 9, -1, 2, 8, 768, P, 0), -3),
+        ("stonk_word_embed_grad", (P, 768, P, 0, P, 768, 9, -1, 0, 8, 768, P, 0), 0),
+        ("stonk_gather_rows_bf16", (P, 768, 0, P, P, 768, 768, 4, 0), -1),
+        ("stonk_gather_rows_bf16", (P, 768, P, P, P, 768, 12, 4, 0), -3),
+        ("stonk_gather_rows_bf16", (P, 772, P, P, P, 768, 768, 4, 0), -3),    # bf16 source: ld_src % 8
+        ("stonk_gather_rows_bf16", (P, 768, P, P, P, 772, 768, 4, 0), -3),
+        ("stonk_gather_rows_bf16", (P, 768, P, P, P, 768, 768, -1, 0), -3),
+        ("stonk_gather_rows_bf16", (P, 768, P, P, P, 768, 768, 0, 0), 0),
+        ("stonk_scatter_rows_bf16", (P, 768, P, 0, P, 768, 768, 0), -1),
+        ("stonk_scatter_rows_bf16", (P, 772, P, P, P, 768, 768, 0), -3),      # bf16 source: ld_src % 8 ...
+        ("stonk_scatter_rows_bf16", (P, 768, P, P, P, 772, 768, 0), -3),
+        ("stonk_scatter_rows_f32_to_bf16", (0, 768, P, P, P, 768, 768, 0), -1),
+        ("stonk_scatter_rows_f32_to_bf16", (P, 770, P, P, P, 768, 768, 0), -3),   # ... fp32 source: ld_src % 4
+        ("stonk_scatter_rows_f32_to_bf16", (P, 772, P, P, P, 772, 768, 0), -3),   # (772 passes for the source; ld_dst % 8)
+        ("stonk_softmax_xent_fwd_bwd", (0, 16, 8, 8, P, P, P, 0, 0, 1.0, 4, P, 0), -1),
+        ("stonk_softmax_xent_fwd_bwd", (P, 16, 8, 8, P, P, P, 0, 0, 1.0, -1, P, 0), -1),
+        ("stonk_softmax_xent_fwd_bwd", (P, 16, 9, 8, P, P, P, 0, 0, 1.0, 4, P, 0), -2),
+        ("stonk_softmax_xent_fwd_bwd", (P, 10, 8, 8, P, P, P, 0, 0, 1.0, 4, P, 0), -2),       # fp32 rows: ld % 4
+        ("stonk_softmax_xent_fwd_bwd", (P, 12, 8, 8, P, P, P, P, 12, 1.0, 4, P, 0), -2),      # (12 passes; ld_d % 8)
+        ("stonk_softmax_xent_f16_fwd_bwd", (0, 16, 8, 8, P, P, P, 0, 0, 1.0, 4, P, 0), -1),
+        ("stonk_softmax_xent_f16_fwd_bwd", (P, 12, 8, 8, P, P, P, 0, 0, 1.0, 4, P, 0), -2),   # fp16 rows: ld % 8
+        ("stonk_softmax_xent_f16_fwd_bwd", (P, 16, 8, 8, P, P, P, P, 4, 1.0, 4, P, 0), -2),
+        ("stonk_softmax_xent_f16_fwd_bwd", (8, 16, 8, 8, P, P, P, 0, 0, 1.0, 4, P, 0), -3),   # ... and a 16-byte aligned base
+        ("stonk_row_topk_f32", (0, 16, 8, 0, P, 4, 2, P, P, P, 0, 0, 0), -1),
+        ("stonk_row_topk_f32", (P, 16, 8, P, P, 4, 2, P, P, P, 0, 0, 0), -1),                 # targets without rank / logit
+        ("stonk_row_topk_f32", (P, 16, 8, 0, P, 4, 17, P, P, P, 0, 0, 0), -2),
+        ("stonk_row_topk_f32", (P, 16, 8, 0, P, 4, 9, P, P, P, 0, 0, 0), -2),                 # k > ncols
+        ("stonk_row_topk_f32", (P, 7, 8, 0, P, 4, 2, P, P, P, 0, 0, 0), -1),
+        ("stonk_row_topk_f32", (P, 16, 8, 0, P, 0, 2, P, P, P, 0, 0, 0), 0),
+        ("stonk_row_topk_f16", (P, 16, 8, 0, P, 4, 0, P, P, P, 0, 0, 0), -2),
+        ("stonk_row_topk_f16", (P, 16, 8, 0, P, -1, 2, P, P, P, 0, 0, 0), -1),
+        ("stonk_row_topk_f16", (P, 16, 8, 0, P, 0, 2, P, P, P, 0, 0, 0), 0),
+        ("stonk_small_linear_fwd", (P, 768, 0, 0, P, 4, 2, 768, 0, 0), -1),
+        ("stonk_small_linear_fwd", (P, 760, P, 0, P, 4, 2, 768, 0, 0), -2),
+        ("stonk_small_linear_fwd", (P, 768, P, 0, P, 0, 2, 768, 0, 0), 0),
+        ("stonk_small_linear_bwd", (P, 0, P, 768, P, 0, 0, 0, 0, 0, 4, 2, 768, 0, 0), -1),
+        ("stonk_small_linear_bwd", (P, 0, P, 768, P, P, 0, 0, 0, 0, 4, 2, 768, TANH, 0), -1),  # tanh needs y
+        ("stonk_small_linear_bwd", (P, 0, P, 768, P, P, 0, 0, 0, 0, 4, 0, 768, 0, 0), -2),
+        ("stonk_small_linear_bwd", (P, 0, P, 768, P, P, 0, 0, 0, 0, 0, 2, 768, 0, 0), 0),
+        ("stonk_gelu_bwd_bf16", (P, P, P, 12, 0), -1),
+        ("stonk_gelu_bwd_bf16", (P, P, P, 0, 0), 0),
+        ("stonk_dropout_f32", (P, P, 8, 1.0, 0, 0), -1),
+        ("stonk_dropout_f32", (P, P, 0, 0.1, 0, 0), 0),
+        ("stonk_sumsq_f32_plus", (0, 8, P, P, 257, 0, 0, 0), -1),
+        ("stonk_sumsq_f32_plus", (P, 8, P, P, 257, 0, 1, 0), -1),        # extras announced, none given
+        ("stonk_sumsq_f32_plus", (P, 8, P, P, 256, 0, 0, 0), -1),        # a short workspace (256 slots + the ticket)
+        ("stonk_sumsq_f32_plus", (8, 8, P, P, 257, 0, 0, 0), -3),
+        ("stonk_sumsq_f32_plus", (P, 0, P, P, 257, 0, 0, 0), 0),
+        ("stonk_sumsq_f32", (P, 8, P, P, 256, 0), -1),
+        ("stonk_sumsq_f32", (P, 0, P, P, 257, 0), 0),
+        ("stonk_adamw_step", (P, P, P, P, 0, 6, 1e-3, 0.9, 0.999, 1e-8, 0.0, 0.1, 0.001, 0, 1.0, 1.0, 0, 0, 0, 0), -1),
+        ("stonk_adamw_step", (P, P, P, P, 0, 8, 1e-3, 0.9, 0.999, 1e-8, 0.0, 0.1, 0.001, 0, 1.0, 1.0, 0, 1, 0, 0), -1),
+        ("stonk_adamw_step", (8, P, P, P, 0, 8, 1e-3, 0.9, 0.999, 1e-8, 0.0, 0.1, 0.001, 0, 1.0, 1.0, 0, 0, 0, 0), -3),
+        ("stonk_adamw_step", (P, P, P, P, 0, 8, 1e-3, 0.9, 0.999, 1e-8, 0.0, 0.0, 0.001, 0, 1.0, 1.0, 0, 0, 0, 0), -1),
+        ("stonk_adamw_step", (P, P, P, P, 0, 0, 1e-3, 0.9, 0.999, 1e-8, 0.0, 0.1, 0.001, 0, 1.0, 1.0, 0, 0, 0, 0), 0),
+        ("stonk_scale_f32", (0, 8, 2.0, 0), -1),
+        ("stonk_scale_f32", (P, 0, 2.0, 0), 0),
+        ("stonk_cast_f32_to_bf16", (P, 0, 8, 0), -1),
+        ("stonk_cast_f32_to_bf16", (P, 4, 8, 0), -3),
+        ("stonk_cast_f32_to_bf16", (P, P, 0, 0), 0),
+        ("stonk_transpose_bf16", (0, 64, P, 128, 65, 64, 0, 0, 0), -1),
+        ("stonk_transpose_bf16", (P, 64, P, 128, 65, 12, 0, 0, 0), -3),
+        ("stonk_transpose_bf16", (P, 68, P, 128, 65, 64, 0, 0, 0), -3),
+        ("stonk_transpose_bf16", (P, 64, P, 72, 65, 64, 0, 0, 0), -2),      # ld_out below the 64-row round-up (128)
+        ("stonk_transpose_bf16", (P, 64, P, 128, 0, 64, 0, 0, 0), 0),
+        ("stonk_transpose_f32_to_bf16", (P, 0, 65, 64, 128, 0), -1),
+        ("stonk_transpose_f32_to_bf16", (P, P, 65, 12, 128, 0), -3),
+        ("stonk_transpose_f32_to_bf16", (P, P, 65, 64, 68, 0), -3),
+        ("stonk_transpose_f32_to_bf16", (P, P, 65, 64, 72, 0), -2),
+        ("stonk_transpose_f32_to_bf16", (P, P, 0, 64, 128, 0), 0),
+    ]
+    got = [(name, args, getattr(lib, name)(*args)) for name, args, _ in table]
+    wrong = [(name, args, code, want) for (name, args, code), (_, _, want) in zip(got, table) if code != want]
+    assert not wrong, wrong
+    assert lib.stonk_layernorm_bwd_workspace_floats(9, 768) == 3 * 2 * 768 and lib.stonk_layernorm_bwd_workspace_floats(4, 0) == 0
     with pytest.raises(_hip.StonkHipError):
         _hip.check(-2, "x")
 
@@ -460,6 +578,25 @@ def test_written_out_kernels_use_no_scratch():
         attn = kr.kernel_resources(os.path.join(csrc, obj))
         bad = [(k["name"], k["scratch"]) for k in attn if k["scratch"] or k.get("vgpr_spill", 0) or k.get("sgpr_spill", 0)]
         assert len(attn) == count and not bad, (obj, len(attn), bad)
+
+
+def test_rowwise_objects_hold_every_kernel_instance():
+    """The six row-wise sources reach their template instances through host-side dispatchers (H -> lane width or chunks per
+    lane, run-time switches -> template arguments, source type -> kernel): an instance a dispatcher no longer names is not
+    compiled, one named twice is still one. The census of the built objects, and no scratch or VGPR spill in any of them.
+    (SGPR spills are not asserted: joint_embed_ln_kernel<8> and the row_topk kernels have some.)"""
+    import importlib.util
+    import subprocess
+
+    spec = importlib.util.spec_from_file_location("kernel_resources", os.path.join(ROOT, "tools", "kernel_resources.py"))
+    kr = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(kr)
+    r = subprocess.run(["make", "-C", ROOT, "-j8"], capture_output=True, text=True, timeout=1500)
+    assert r.returncode == 0, r.stderr[-2000:]
+    for obj, count in (("norm.o", 32), ("loss.o", 8), ("small.o", 8), ("optim.o", 9), ("topk.o", 10), ("text_embed.o", 1)):
+        ks = kr.kernel_resources(os.path.join(ROOT, "stonkgs_amd", "csrc", obj))
+        bad = [(k["name"], k["scratch"], k.get("vgpr_spill", 0)) for k in ks if k["scratch"] or k.get("vgpr_spill", 0)]
+        assert len(ks) == count and len({k["name"] for k in ks}) == count and not bad, (obj, len(ks), bad)
 
 
 def test_generated_gemm_loop_is_up_to_date():

@@ -105,35 +105,52 @@ def test_layernorm_fwd_bwd_fp64(hip, rows, H):
         check_f32(f"{tag}.dbeta.{route}", db, *want["dbeta"])
 
 
-@pytest.mark.parametrize("p", [0.1, 0.5])
-@pytest.mark.parametrize("rows,H", [(4100, 768), (4100, 640), (5, 1536)])
-def test_layernorm_dropout_exact_masks(hip, rows, H, p):
+# (rows, H, p, which): which of the two dropouts of the backward is on - "in" = STONK_LN_DROPOUT (dy is the gradient of a
+# dropped-out y), "out" = dx_drop is asked for, "both". The (4100, .) cases give a wave a second row; (9, .) = three
+# workgroups, the last with one live wave, at the three lane widths (512 / 768 / 1024: every <EPL, in, out> instance of the
+# lane backward and both of the lane forward) and at 640 for the generic kernels' run-time switches.
+_LN_DROP_CASES = ([(rows, H, p, "both") for rows, H in [(4100, 768), (4100, 640), (5, 1536)] for p in (0.1, 0.5)]
+                  + [(9, H, 0.1, which) for H in (512, 768, 1024, 640) for which in ("in", "out", "both")])
+
+
+@pytest.mark.parametrize("rows,H,p,which", _LN_DROP_CASES,
+                         ids=[f"{r}-{H}-{p}" + ("" if r != 9 else f"-{w}") for r, H, p, w in _LN_DROP_CASES])
+def test_layernorm_dropout_exact_masks(hip, rows, H, p, which):
     c = _LnCase(rows, H)
-    tag = f"lndrop[{rows}x{H},p={p}]"
+    tag = f"lndrop[{rows}x{H},p={p},{which}]"
     seed_in, seed_out = 77, 78
+    d_in, d_out = which in ("in", "both"), which in ("out", "both")
     k_in, k_out = _keep(range(rows), H, seed_in, p), _keep(range(rows), H, seed_out, p)
     inv = 1.0 / (1.0 - _p32(p))
-    x, dy, gamma, beta = c.x.cuda(), c.dy.cuda(), c.gamma.cuda(), c.beta.cuda()
-    y, mean, rstd = _ln_fwd(hip, c, x, gamma, beta, flags=hip.LN_DROPOUT, p=p, seed=seed_in)
-    r64, r32 = c.ref(torch.float64, k_in, inv), c.ref(torch.float32, k_in, inv)
-    yc = y.cpu()
-    assert (yc[~k_in] == 0).all(), "an element the generator drops is not zero"
     zero64, zero32 = torch.zeros((), dtype=torch.float64), torch.zeros(())
-    check_bf16(f"{tag}.y", y, torch.where(k_in, r64["y"] * inv, zero64), torch.where(k_in, r32["y"] * inv, zero32))
+    x, dy, gamma, beta = c.x.cuda(), c.dy.cuda(), c.gamma.cuda(), c.beta.cuda()
+    flags = hip.LN_DROPOUT if d_in else 0
+    y, mean, rstd = _ln_fwd(hip, c, x, gamma, beta, flags=flags, p=p, seed=seed_in)
+    if d_in:
+        r64, r32 = c.ref(torch.float64, k_in, inv), c.ref(torch.float32, k_in, inv)
+        assert (y.cpu()[~k_in] == 0).all(), "an element the generator drops is not zero"
+        check_bf16(f"{tag}.y", y, torch.where(k_in, r64["y"] * inv, zero64), torch.where(k_in, r32["y"] * inv, zero32))
+    else:
+        r64, r32 = c.ref(torch.float64), c.ref(torch.float32)
+        check_bf16(f"{tag}.y", y, r64["y"], r32["y"])
     check_f32(f"{tag}.mean", mean, r64["mean"], r32["mean"])
     check_f32(f"{tag}.rstd", rstd, r64["rstd"], r32["rstd"])
 
     dg0, db0 = _randn((H,), 5, 3.0), _randn((H,), 6, 3.0)
     dg, db = dg0.cuda(), db0.cuda()
     ws = torch.empty(int(hip.lib().stonk_layernorm_bwd_workspace_floats(rows, H)), device="cuda")
-    dx, dxd = _ln_bwd(hip, c, dy, x, mean, rstd, gamma, dg, db, ws, flags=hip.LN_DROPOUT, p_in=p, seed_in=seed_in, p_out=p,
-                      seed_out=seed_out, drop=True)
-    check_bf16(f"{tag}.dx", dx, r64["dx"], r32["dx"])       # fp64 backward of dy masked by the oracle (seed_in)
-    assert (dxd.cpu()[~k_out] == 0).all(), "dx_drop: an element the generator drops (seed_out) is not zero"
-    check_bf16(f"{tag}.dx_drop", dxd, torch.where(k_out, r64["dx"] * inv, zero64),
-               torch.where(k_out, r32["dx"] * inv, zero32))
+    dx, dxd = _ln_bwd(hip, c, dy, x, mean, rstd, gamma, dg, db, ws, flags=flags, p_in=p, seed_in=seed_in, p_out=p,
+                      seed_out=seed_out, drop=d_out)
+    check_bf16(f"{tag}.dx", dx, r64["dx"], r32["dx"])       # fp64 backward of dy, masked by the oracle (seed_in) with "in"
+    if d_out:
+        assert (dxd.cpu()[~k_out] == 0).all(), "dx_drop: an element the generator drops (seed_out) is not zero"
+        check_bf16(f"{tag}.dx_drop", dxd, torch.where(k_out, r64["dx"] * inv, zero64),
+                   torch.where(k_out, r32["dx"] * inv, zero32))
     check_f32(f"{tag}.dgamma", dg, dg0.double() + r64["dgamma"], dg0 + r32["dgamma"])
     check_f32(f"{tag}.dbeta", db, db0.double() + r64["dbeta"], db0 + r32["dbeta"])
+    if which == "out":   # dx is the unmasked backward: the very bits of a call that asks for no dx_drop
+        dx_plain, _ = _ln_bwd(hip, c, dy, x, mean, rstd, gamma, dg0.cuda(), db0.cuda(), ws)
+        assert torch.equal(dx, dx_plain)
 
 
 # ---- stonk_joint_embed_ln_fwd ----------------------------------------------------------------------------------------
