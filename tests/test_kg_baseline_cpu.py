@@ -63,11 +63,21 @@ class Restatement:
 
 
 def train_restated(pooled, labels, order_steps, weight, bias, cw, lr, seed, run, p, first_step=0, dtype=torch.float64):
-    """Walk ``order_steps`` ([steps, batch] int, -1 padded) with the kernel's keep masks. Returns (Restatement, losses)."""
+    """Walk ``order_steps`` ([steps, batch] int, -1 padded) with the kernel's keep masks. Returns (Restatement, losses).
+    A step whose rows are all padding has the loss 0 / 0 = NaN and updates nothing (csrc/kg_baseline.hip, step (D)); it
+    still counts as a global step: the masks of the steps after it are keyed by ``first_step + s``, and AdamW's bias
+    corrections of the steps after it use the step number that counts it (the optimizer's own counter is advanced).
+    ``first_step`` > 0 only offsets the masks: a run restated from the middle starts with fresh moments."""
     rs = Restatement(weight, bias, cw, lr, dtype)
     losses = []
     for s, row in enumerate(np.asarray(order_steps)):
         live = row >= 0
+        if not live.any():
+            assert rs.optimizer.state, "an all-padding step before the first real one: torch's AdamW has no counter yet"
+            for st in rs.optimizer.state.values():
+                st["step"] += 1
+            losses.append(float("nan"))
+            continue
         mask = kgb.dropout_keep_mask(seed, run, first_step + s, len(row), pooled.shape[1], p)[live] if p > 0 else None
         losses.append(rs.step(pooled[row[live]], labels[row[live]], mask, p))
     return rs, np.array(losses)

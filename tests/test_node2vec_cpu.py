@@ -94,31 +94,43 @@ def _draw(key, attempt, which):
 
 
 def group_nodes(walks, w, t, n, window, negatives, alias_thr, alias_idx, seedkey):
-    """(contexts, targets) of group (w, t): targets[0] is the centre, the rest its noise nodes (centre hits skipped)."""
+    """(contexts, targets) of group (w, t): targets[0] is the centre, the rest its noise nodes (centre hits skipped).
+    The skip rules of csrc/node2vec.hip's header: a centre outside [0, n) skips the group - ([], []) -, a context outside
+    [0, n) the pair, an alias target outside [0, n) that noise node."""
     row = walks[w]
     L = len(row)
     c = int(row[t])
+    if not 0 <= c < n:
+        return [], []
     key = _h(_h(seedkey + w) ^ ((t * 0x9E3779B1) & M32))
     b = 1 + _draw(key, 0, 0) % window
-    ctx = [int(row[u]) for u in range(max(t - b, 0), min(t + b, L - 1) + 1) if u != t]
+    ctx = [int(row[u]) for u in range(max(t - b, 0), min(t + b, L - 1) + 1) if u != t and 0 <= int(row[u]) < n]
     tgt = [c]
     for j in range(negatives):
         slot = (_draw(key, j + 1, 0) * n) >> 32
         node = slot if _draw(key, j + 1, 1) < int(alias_thr[slot]) else int(alias_idx[slot])
-        if node != c:
+        if node != c and 0 <= node < n:
             tgt.append(node)
     return ctx, tgt
 
 
-def sgns_ref(walks, w_in, w_out, groups, window, negatives, alias_thr, alias_idx, lr, seed, loss):
+def reduced_window(w, t, window, seed):
+    """b of group (w, t): the kernel takes contexts from [t - b, t + b]."""
+    key = _h(_h(_h(seed ^ SGNS_SALT) + w) ^ ((t * 0x9E3779B1) & M32))
+    return 1 + _draw(key, 0, 0) % window
+
+
+def sgns_ref(walks, w_in, w_out, groups, window, negatives, alias_thr, alias_idx, lr, seed, loss, nodes=group_nodes):
     """stonk_sgns_step's groups one after the other, in the dtype of w_in (float64: the reference; float32: the error of the
-    number format). Mini-batch inside a group: every g from the rows as read first, then the adds. loss: [sum, count]."""
+    number format). Mini-batch inside a group: every g from the rows as read first, then the adds. loss: [sum, count].
+    A group whose centre is outside [0, N), or that has no valid context, adds nothing. ``nodes``: the group's node lists
+    (tests/graph_ref.py swaps in deliberately wrong ones to show that its cases tell them apart)."""
     dt = w_in.dtype.type
     n = w_in.shape[0]
     seedkey = _h(seed ^ SGNS_SALT)
     lr = dt(lr)
     for w, t in groups:
-        ctx, tgt = group_nodes(walks, w, t, n, window, negatives, alias_thr, alias_idx, seedkey)
+        ctx, tgt = nodes(walks, w, t, n, window, negatives, alias_thr, alias_idx, seedkey)
         if not ctx:
             continue
         C, T = w_in[ctx], w_out[tgt]
