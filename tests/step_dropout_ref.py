@@ -241,6 +241,43 @@ def oracle_cls_step(sd, cfg, table, inputs, labels, dropout, autocast: bool = Fa
     return {"loss": float(out["loss"].detach())}, grads
 
 
+def oracle_text_step(sd, cfg, batch, dropout, autocast: bool = False):
+    """The same for the text-only classifier (tests/test_text_embed_cpu.text_classifier, which transformers'
+    BertForSequenceClassification pins at p = 0): ({"loss": float}, gradients of EVERY parameter, the word table included -
+    its pad row is read detached and stays zero)."""
+    from tests.test_text_embed_cpu import text_classifier
+
+    names = list(sd)
+    params = {k: sd[k].detach().clone().requires_grad_(True) for k in names}
+    with torch.autocast("cpu", dtype=torch.bfloat16) if autocast else contextlib.nullcontext():
+        out = text_classifier(params, cfg, batch["input_ids"], batch["attention_mask"], batch["token_type_ids"],
+                              batch["labels"], dropout=dropout)
+    grads = torch.autograd.grad(out["loss"], [params[k] for k in names], allow_unused=True)
+    grads = {k: (torch.zeros_like(sd[k]) if g is None else g.detach()) for k, g in zip(names, grads)}
+    return {"loss": float(out["loss"].detach())}, grads
+
+
+def adamw_update(sd, grads, state, base_lr: float, max_steps: int, max_grad_norm: float = 1.0, betas=(0.9, 0.999),
+                 eps: float = 1e-8) -> None:
+    """The optimizer half of ``orc.train_step`` (clip by the global norm, AdamW without weight decay, linear schedule) from
+    gradients the caller has: the mean over the micro-batches of an accumulation window, or a model ``train_step`` does not
+    know. Updates `sd` and `state` (``orc.AdamState``) in place."""
+    total = float(torch.sqrt(sum((g.double() ** 2).sum() for g in grads.values())).float())
+    coef = min(1.0, max_grad_norm / (total + 1e-6)) if max_grad_norm and max_grad_norm > 0 else 1.0
+    lr = orc.linear_schedule_lr(base_lr, state.step, max_steps)
+    state.step += 1
+    b1, b2 = betas
+    bc1, bc2 = 1 - b1 ** state.step, 1 - b2 ** state.step
+    with torch.no_grad():
+        for k, g in grads.items():
+            g = g * coef
+            m = state.m.setdefault(k, torch.zeros_like(sd[k]))
+            v = state.v.setdefault(k, torch.zeros_like(sd[k]))
+            m.mul_(b1).add_(g, alpha=1 - b1)
+            v.mul_(b2).addcmul_(g, g, value=1 - b2)
+            sd[k].addcdiv_(m, (v.sqrt() / (bc2 ** 0.5)).add_(eps), value=-lr / bc1)
+
+
 def rel(a, b) -> float:
     """Relative L2 distance of `a` from the reference `b`; a reference that is analytically zero (key.bias) is compared on
     the absolute scale tests/test_model_gpu.py uses."""

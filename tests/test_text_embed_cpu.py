@@ -34,17 +34,18 @@ def text_state_dict(cfg, num_labels=3, seed=11):
     return sd
 
 
-def text_classifier(sd, cfg, input_ids, attention_mask=None, token_type_ids=None, labels=None):
-    """BertForSequenceClassification.forward with dropout off, from the oracle's pieces: embeddings of token ids, the
-    encoder, the pooler line and a classifier. nn.Embedding(padding_idx=0) never accumulates a gradient into the pad row:
-    the row is read detached."""
+def text_classifier(sd, cfg, input_ids, attention_mask=None, token_type_ids=None, labels=None, dropout=None):
+    """BertForSequenceClassification.forward from the oracle's pieces: embeddings of token ids, the encoder, the pooler line
+    and a classifier. nn.Embedding(padding_idx=0) never accumulates a gradient into the pad row: the row is read detached.
+    `dropout` None: dropout off, no operation added; else a mask provider (`orc._drop`; tests/step_dropout_ref.py) for the
+    embeddings, every encoder site and the pooled vector."""
     w = sd[WORD]
     sd = dict(sd)
     sd[WORD] = torch.cat([w[:PAD], w[PAD:PAD + 1].detach(), w[PAD + 1:]])
-    x = orc.bert_embeddings(sd, "bert.embeddings", cfg, input_ids=input_ids, token_type_ids=token_type_ids)
-    seq = orc.bert_encoder(x, sd, "bert.encoder", cfg, cfg.num_hidden_layers, attention_mask)
+    x = orc.bert_embeddings(sd, "bert.embeddings", cfg, input_ids=input_ids, token_type_ids=token_type_ids, dropout=dropout)
+    seq = orc.bert_encoder(x, sd, "bert.encoder", cfg, cfg.num_hidden_layers, attention_mask, dropout=dropout)
     pooled = torch.tanh(F.linear(seq[:, 0], sd["bert.pooler.dense.weight"], sd["bert.pooler.dense.bias"]))
-    logits = F.linear(pooled, sd["classifier.weight"], sd["classifier.bias"])
+    logits = F.linear(orc._drop(pooled, dropout, ("classifier", 0)), sd["classifier.weight"], sd["classifier.bias"])
     out = {"logits": logits, "pooler_output": pooled}
     if labels is not None:
         out["loss"] = F.cross_entropy(logits, labels.view(-1))
