@@ -174,7 +174,15 @@ int stonk_input_attribution(const void* dsum, int64_t ld, const int64_t* input_i
  * positions: the decoders; position 0: the pooler), on which alone the last layer's row-wise feed-forward block, the pooler
  * and the head transform need to run: read_rows [B*S] (packed row of the j-th read row, -1 past their count),
  * read_of_pos [B*S] (index into read_rows of a padded position, or -1), read_offsets [B+1] ([B] = their count;
- * read_rows[read_offsets[b]] is position 0 of sequence b). workspace: device ints, stonk_unpad_workspace_ints(B) of them. */
+ * read_rows[read_offsets[b]] is position 0 of sequence b). workspace: device ints, stonk_unpad_workspace_ints(B) of them
+ * (= 3 B; it need not be zeroed). `half` is an argument of its own, 0 <= half <= S: a text label is read iff s < half, an
+ * entity label iff half <= s < 2 half (both label arrays are [B, half]); positions from 2 half on are kept by their mask
+ * word alone, and with half == 0 (the text-only baseline) neither label pointer is read. Any mask word != 0 is live;
+ * row_mask carries the raw word. A sequence's packed rows are its read rows in position order, then its other kept rows
+ * in position order.
+ * Refused before any launch, in this order: attention_mask / row_of_pos / pos_of_row / seq_offsets / row_mask / workspace
+ * null, or some but not all of the three read outputs given (STONK_EINVAL); B < 0, S <= 0, half < 0, half > S,
+ * B S >= 2^31 (STONK_ESHAPE); ws_ints < 3 B (STONK_EINVAL). B == 0 returns STONK_OK. */
 int64_t stonk_unpad_workspace_ints(int B);
 int stonk_unpad_plan(const int64_t* attention_mask, const int64_t* text_labels, const int64_t* ent_labels, int B, int S,
                      int half, int* row_of_pos, int* pos_of_row, int* seq_offsets, int64_t* row_mask, int* read_rows,
@@ -280,7 +288,11 @@ int stonk_cast_f32_to_bf16(const float* x, void* y, int64_t n, void* stream);
  * as the reference masks the padded sequence; 80 % -> mask_id, 10 % kept, 10 % uniform id in [0, vocab_*-1]; labels =
  * original id there, -100 elsewhere. Counter-based random stream (seed, row, half, position), restated bit for bit by
  * oracle/masking_oracle.py. Replaces ref:src/stonkgs/data/indra_for_pretraining.py:33-77 (replace_mlm_tokens), whose
- * own Mersenne-Twister draws stay reproducible on the host path (stonkgs_amd/data.py). */
+ * own Mersenne-Twister draws stay reproducible on the host path (stonkgs_amd/data.py). Ids, labels and mask_id are
+ * int64 words and pass through unchanged whatever their size; a random id is below vocab_* < 2^32. One workgroup per
+ * (row, half) holds the half's keys in LDS: half <= 8192.
+ * Refused before any launch, in this order: a null pointer (STONK_EINVAL); B < 0, half <= 0, S != 2 half, half > 8192
+ * (STONK_ESHAPE); vocab_* <= 0 or >= 2^32 (STONK_EINVAL); k_* < 0 or > half (STONK_EINVAL). B == 0 returns STONK_OK. */
 int stonk_mlm_mask(const int64_t* ids_in, int64_t* ids_out, int64_t* text_labels, int64_t* ent_labels, int B, int S,
                    int half, int64_t vocab_text, int64_t vocab_ent, int64_t mask_id, int k_text, int k_ent, uint32_t seed,
                    void* stream);
@@ -289,8 +301,16 @@ int stonk_mlm_mask(const int64_t* ids_in, int64_t* ids_out, int64_t* text_labels
  * walks [n_nodes, walk_len] (2 * walk_len + 2 == half) -> ids_out / attention_out / type_out [B,S], nsp_out [B]. Entity
  * half = walks[source] [SEP] walks[target] [SEP]; with probability negative_rate a row takes the entity half of another
  * row of the batch and NSP label 1 (the reference appends 25 % such rows offline: the same 1 in 5). A node index outside
- * the table sets bit 0 of *err_flag (the reference raises KeyError). Replaces
- * ref:src/stonkgs/data/indra_for_pretraining.py:190-239 (row assembly) and :80-126 (negative NSP samples). */
+ * the table - of the row itself or of a negative's partner row - sets bit 0 of *err_flag (the reference raises KeyError)
+ * and writes 0 at every entity position it feeds; the [SEP]s and every other element are written as usual. Replaces
+ * ref:src/stonkgs/data/indra_for_pretraining.py:190-239 (row assembly) and :80-126 (negative NSP samples).
+ * negative_rate is a FLOAT: row b is a negative iff B > 1 and its 32-bit draw is below
+ * (uint32)((double)negative_rate * 2^32 + 0.5) - for 0.2f that is 858993472, not the 858993459 of the double 0.2; a
+ * restatement must round the rate to float32 first. A negative's partner is drawn uniformly from [0, B); a row that
+ * draws itself takes (b + 1) % B.
+ * Refused before any launch, in this order: a null pointer (STONK_EINVAL); B < 0, half <= 0, S != 2 half,
+ * 2 walk_len + 2 != half, n_nodes <= 0 (STONK_ESHAPE); negative_rate < 0 or >= 1 as a float (STONK_EINVAL). B == 0
+ * returns STONK_OK. */
 int stonk_assemble_rows(const int64_t* text_ids, const int64_t* text_attention, const int64_t* source,
                         const int64_t* target, const int64_t* walks, int64_t n_nodes, int walk_len, int64_t* ids_out,
                         int64_t* attention_out, int64_t* type_out, int64_t* nsp_out, int B, int S, int half,
