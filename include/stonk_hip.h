@@ -57,6 +57,24 @@ int stonk_gemm_nt_bf16(const void* A, int64_t lda, const void* B, int64_t ldb, v
  * Autograd's weight/bias gradients of every nn.Linear on the path. */
 int stonk_gemm_tn_bf16(const void* dY, int64_t lda, const void* X, int64_t ldb, float* dW, int64_t ldc, float* dbias,
                        int M, int N, int K, float alpha, int split_k, const int* k_dev, void* stream);
+/* Up to 4 accumulating weight-gradient launches of the four-wave 256x256 kernel as ONE launch: gradients whose operands are
+ * ready together share the CUs, so each is split over fewer K shares (fewer float atomics per element of dW). `problems` is
+ * a HOST array of n descriptors (fields as the arguments of stonk_gemm_tn_bf16; read before the call returns). Per problem:
+ * M', N' % 256 == 0, lda / ldb % 64 == 0, ldc >= N', M' * ldc * 4 < 2^31, else STONK_ESHAPE. cu_cap: the CUs' worth of
+ * workgroups the launch may take (1 .. 1024; 0 = every CU of the device). One K split for all: the largest with
+ * sum(tiles) * split <= cu_cap and split <= (K tiles of a problem) / 8 for every problem. n > 4, or more 256x256 tiles in
+ * all than cu_cap: STONK_ESHAPE - launch the members one by one. The result differs from n stonk_gemm_tn_bf16 launches only
+ * in the order of the fp32 additions. */
+typedef struct StonkTnProblem {
+  const void* dY; int64_t lda;
+  const void* X; int64_t ldb;
+  float* dW; int64_t ldc;
+  float* dbias;
+  const int* k_dev;
+  int M, N, K;
+  float alpha;
+} StonkTnProblem;
+int stonk_gemm_tn_bf16_group(const StonkTnProblem* problems, int n, int cu_cap, void* stream);
 /* The same product STORED: dW = alpha * dY^T . X, db = alpha * colsum(dY) - whatever dW / db held before is overwritten,
  * and every element is defined even when *k_dev == 0 (zeros). Only for a launch that stonk_gemm_tn_bf16's routing leaves
  * with ONE K split (split_k == 1, or a split_k <= 0 whose automatic split comes out as 1; not -1): one producer per

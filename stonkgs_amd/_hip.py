@@ -44,6 +44,7 @@ _SIGNATURES = {
     "stonk_gemm_tn_bf16": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _f32, _i32, _vp, _vp],
     "stonk_gemm_tn_bf16_store": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _f32, _i32, _vp, _vp],
     "stonk_gemm_tn_bf16_store_sumsq": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _i64, _vp],
+    "stonk_gemm_tn_bf16_group": [_vp, _i32, _i32, _vp],   # (a HOST array of TnProblem first: `tn_problems`)
     "stonk_layernorm_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _i32, _f32, _u32, _vp],
     "stonk_layernorm_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _u32, _f32, _u32,
                             _vp, _i64, _vp],
@@ -126,6 +127,23 @@ _SIGNATURES = {
 
 class StonkHipError(RuntimeError):
     pass
+
+
+class TnProblem(C.Structure):
+    """StonkTnProblem of include/stonk_hip.h: one member of a stonk_gemm_tn_bf16_group launch."""
+    _fields_ = [("dY", _vp), ("lda", _i64), ("X", _vp), ("ldb", _i64), ("dW", _vp), ("ldc", _i64), ("dbias", _vp),
+                ("k_dev", _vp), ("M", _i32), ("N", _i32), ("K", _i32), ("alpha", _f32)]
+
+
+def tn_problems(members):
+    """A host array of TnProblem from (dY, lda, X, ldb, dW, ldc, dbias, M, N, K, alpha, k_dev) tuples of raw addresses and
+    sizes - the leading arguments of stonk_gemm_tn_bf16 without split_k. Pass it as the first argument of
+    stonk_gemm_tn_bf16_group, with len() as the second."""
+    arr = (TnProblem * len(members))()
+    for q, (dY, lda, X, ldb, dW, ldc, dbias, M, N, K, alpha, k_dev) in zip(arr, members):
+        q.dY, q.lda, q.X, q.ldb, q.dW, q.ldc, q.dbias, q.k_dev = dY, lda, X, ldb, dW, ldc, dbias, k_dev
+        q.M, q.N, q.K, q.alpha = M, N, K, alpha
+    return arr
 
 
 _lib = None

@@ -28,6 +28,15 @@ struct GemmArgs {
   uint32_t seed;      // already mixed (stonk_seed_mix)
 };
 
+// Argument block of the grouped weight-gradient kernel (gemm_tn_a4_group.hip): problem i owns the block indices
+// first[i] .. first[i] + items[i] - 1, one work item each (items[i] = its tiles x prob[i].split_k); first[] ascends.
+struct TnGroupArgs {
+  static constexpr int MAX = 4;
+  GemmArgs prob[MAX];
+  int first[MAX], items[MAX];
+  int n;
+};
+
 // blocks b and b+8 share an XCD (round-robin dispatch): give each XCD a contiguous run of tiles so
 // neighbouring tiles (same A row panel / same B column panel) hit the same L2. Bijective for any n.
 __device__ __forceinline__ int xcd_remap(int b, int n) {

@@ -18,12 +18,14 @@
 #include <cstdlib>
 
 #include "gemm_common.h"
+#include "stonk_hip.h"   // (StonkTnProblem)
 
 // persistent 256x256 variant (gemm256.hip, TN = true)
 int stonk_gemm256_tn_launch(const stonk_gemm::GemmArgs& a, hipStream_t st);
 int stonk_gemm_tn_a4_launch(const stonk_gemm::GemmArgs& a, hipStream_t st);
 int stonk_gemm_tn_a4_store_launch(const stonk_gemm::GemmArgs& a, hipStream_t st);   // gemm_tn_a4_store.hip
 int stonk_gemm_tn_a4_store_sumsq_launch(const stonk_gemm::GemmArgs& a, hipStream_t st);   // gemm_tn_a4_store_sumsq.hip (a.aux = the slots)
+int stonk_gemm_tn_a4_group_launch(const stonk_gemm::TnGroupArgs& g, int grid, hipStream_t st);   // gemm_tn_a4_group.hip
 
 namespace {
 
@@ -221,6 +223,17 @@ static long gemm_tn_store_tiles(int M, int N, int split_k) {
   return split_k <= 0 ? (long)((M + 255) / 256) * ((N + 255) / 256) : (long)(M / BM) * (N / BN);
 }
 
+// What the 256x256 kernels ask of a shape beyond the common checks (split_k <= 0 and the grouped entry)
+static int tn_a4_shape_status(int64_t lda, int64_t ldb, int64_t ldc, int M, int N) {
+  STONK_CHECK_ARG(M >= 256 && N >= 256, STONK_ESHAPE);
+  // (operands are addressed per 64-token K tile: 64 rows of either operand must stay inside 32-bit byte offsets)
+  STONK_CHECK_ARG(lda % 64 == 0 && ldb % 64 == 0 && lda < (1L << 23) && ldb < (1L << 23), STONK_ESHAPE);
+  // (the four-wave kernel addresses dW through a buffer resource: a byte range of M * ldc * 4, 32-bit byte offsets, and a
+  // column past N' pushed out of that range - a row stride below N' would let it land in the next row instead)
+  STONK_CHECK_ARG(ldc >= N && (long)M * ldc * 4 < (1L << 31), STONK_ESHAPE);
+  return STONK_OK;
+}
+
 // `tile_sumsq` (store only, nullable): n_slots floats for the per-tile sums of squares - the launch then takes the kernels
 // that leave them
 static int gemm_tn_route(const void* dY, int64_t lda, const void* X, int64_t ldb, float* dW, int64_t ldc, float* dbias,
@@ -241,9 +254,7 @@ static int gemm_tn_route(const void* dY, int64_t lda, const void* X, int64_t ldb
   // one-workgroup-per-CU kernel that takes every CU stalls the other stream until its workgroups retire (the step is 1.5 ms
   // faster with the weight gradients on 160 of the 256 CUs). -1: the older eight-wave 256x256 TN form of gemm256.hip.
   if (split_k <= 0) {
-    STONK_CHECK_ARG(M >= 256 && N >= 256, STONK_ESHAPE);
-    // (operands are addressed per 64-token K tile: 64 rows of either operand must stay inside 32-bit byte offsets)
-    STONK_CHECK_ARG(lda % 64 == 0 && ldb % 64 == 0 && lda < (1L << 23) && ldb < (1L << 23), STONK_ESHAPE);
+    if (const int rc = tn_a4_shape_status(lda, ldb, ldc, M, N)) return rc;
     STONK_CHECK_ARG(split_k >= -1024, STONK_ESHAPE);
     stonk_gemm::GemmArgs g = {};
     g.A = (const bf16*)dY; g.B = (const bf16*)X; g.C = dW; g.bias = dbias; g.k_dev = k_dev;
@@ -288,6 +299,52 @@ extern "C" int stonk_gemm_tn_bf16(const void* dY, int64_t lda, const void* X, in
                                   float* dbias, int M, int N, int K, float alpha, int split_k, const int* k_dev,
                                   void* stream) {
   return gemm_tn_route(dY, lda, X, ldb, dW, ldc, dbias, M, N, K, alpha, split_k, k_dev, stream, false);
+}
+
+// Up to four accumulating launches of the four-wave kernel as ONE (gemm_tn_a4_group.hip): weight gradients whose operands
+// are ready at about the same time share the CU share, so each needs fewer K splits to fill it - fewer float atomics per
+// output element, fewer K-loop prologues, one launch. One common split: the largest sk with sum(tiles) * sk <= cap and
+// sk <= K tiles / 8 of every problem (the single launches' rule), applied to each problem's own K, so that the workgroups
+// of a launch finish together. One work item per workgroup: a group that does not fit the cap unsplit is refused
+// (STONK_ESHAPE) and the caller launches its members one by one.
+extern "C" int stonk_gemm_tn_bf16_group(const StonkTnProblem* problems, int n, int cu_cap, void* stream) {
+  using stonk_gemm::TnGroupArgs;
+  STONK_CHECK_ARG(problems && n > 0 && cu_cap >= 0, STONK_EINVAL);
+  STONK_CHECK_ARG(n <= TnGroupArgs::MAX && cu_cap <= 1024, STONK_ESHAPE);
+  TnGroupArgs g = {};
+  long tiles_all = 0, sk = 1L << 30;
+  for (int i = 0; i < n; ++i) {
+    const StonkTnProblem& q = problems[i];
+    STONK_CHECK_ARG(q.dY && q.X && q.dW, STONK_EINVAL);
+    STONK_CHECK_ARG(q.M > 0 && q.N > 0 && q.K > 0 && q.M % 256 == 0 && q.N % 256 == 0, STONK_ESHAPE);
+    STONK_CHECK_ARG(q.lda % 8 == 0 && q.ldb % 8 == 0, STONK_EALIGN);
+    STONK_CHECK_ARG((uintptr_t)q.dY % 16 == 0 && (uintptr_t)q.X % 16 == 0, STONK_EALIGN);
+    STONK_CHECK_ARG((uintptr_t)q.dW % 4 == 0 && (uintptr_t)q.dbias % 4 == 0, STONK_EALIGN);
+    if (const int rc = tn_a4_shape_status(q.lda, q.ldb, q.ldc, q.M, q.N)) return rc;
+    stonk_gemm::GemmArgs& a = g.prob[i];
+    a.A = (const bf16*)q.dY; a.B = (const bf16*)q.X; a.C = q.dW; a.bias = q.dbias; a.k_dev = q.k_dev;
+    a.lda = q.lda; a.ldb = q.ldb; a.ldc = q.ldc; a.M = q.M; a.N = q.N; a.K = q.K; a.alpha = q.alpha;
+    tiles_all += (long)(q.M / 256) * (q.N / 256);
+    const long by_k = ((q.K + BK - 1) / BK) / 8;
+    sk = by_k < sk ? by_k : sk;
+  }
+  long cap = cu_cap;
+  if (cap == 0) {   // (a cap from the caller needs no device: more workgroups than CUs are late, not wrong)
+    cap = stonk_gemm::cu_count();
+    if (cap <= 0) return (int)hipGetLastError();
+  }
+  STONK_CHECK_ARG(tiles_all <= cap, STONK_ESHAPE);
+  sk = sk < cap / tiles_all ? sk : cap / tiles_all;
+  sk = sk > 0 ? sk : 1;
+  int at = 0;
+  for (int i = 0; i < n; ++i) {
+    g.prob[i].split_k = (int)sk;
+    g.items[i] = (int)((long)(g.prob[i].M / 256) * (g.prob[i].N / 256) * sk);
+    g.first[i] = at;
+    at += i + 1 < n ? (g.items[i] + 7) & ~7 : g.items[i];   // (the next problem starts on a multiple of 8: XCD 0)
+  }
+  g.n = n;
+  return stonk_gemm_tn_a4_group_launch(g, at, (hipStream_t)stream);
 }
 
 // dW = alpha * dY^T . X, db = alpha * colsum(dY): the same kernels with a store epilogue. Only for a launch the routing

@@ -32,11 +32,24 @@
 // slot is a function of the inputs alone, whatever the grid. The accumulator is born after the K loop (one VGPR of the
 // epilogue); the waves meet at one raw barrier per tile behind an LDS word each (16 bytes past the operand images), with
 // no wait for the stores or the next item's operand loads in flight.
+//
+// STONK_TN_A4_GROUP = 1 (gemm_tn_a4_group.hip): the accumulating kernel for up to four problems in ONE launch
+// (stonk_gemm_tn_bf16_group). The argument block is a table of problems; a workgroup finds the problem its block index
+// falls into and is, from there on, workgroup `bid` of a launch of that problem alone on a grid of that problem's own
+// work items (tiles x the common K split): the same tile_split, XCD runs, even K-tile counts and bias duty. One work item
+// per workgroup - the launcher refuses anything else - so no workgroup walks from one problem into another (the K loop
+// prefetches the next item's first K tiles with THIS item's leading dimensions).
 #include "gemm_common.h"
 #ifndef STONK_TN_A4_STORE
 #define STONK_TN_A4_STORE 0
 #endif
-#if STONK_TN_A4_STORE == 2
+#ifndef STONK_TN_A4_GROUP
+#define STONK_TN_A4_GROUP 0
+#endif
+#if STONK_TN_A4_GROUP
+#define STONK_TN_A4_KERNEL gemm_tn_a4_group_kernel
+#define STONK_TN_A4_LAUNCH stonk_gemm_tn_a4_group_launch
+#elif STONK_TN_A4_STORE == 2
 #define STONK_TN_A4_KERNEL gemm_tn_a4_store_sumsq_kernel
 #define STONK_TN_A4_LAUNCH stonk_gemm_tn_a4_store_sumsq_launch
 #elif STONK_TN_A4_STORE
@@ -68,7 +81,22 @@ struct Cursor {     // where an operand stream stands: buffer words + bytes left
   int rem_lo, rem_hi;
 };
 
+#if STONK_TN_A4_GROUP
+__global__ __launch_bounds__(256, 1) void STONK_TN_A4_KERNEL(const TnGroupArgs g) {
+  // (first[] ascends; block indices between a problem's last item and the next problem's first are padding: the launcher
+  // starts every problem on a multiple of 8, so that block index and `bid` name the same XCD)
+  int pi = 0;
+#pragma unroll
+  for (int i = 1; i < TnGroupArgs::MAX; ++i) pi = (i < g.n && (int)blockIdx.x >= g.first[i]) ? i : pi;
+  const GemmArgs& p = g.prob[pi];
+  const int bid = (int)blockIdx.x - g.first[pi];
+  const int G = g.items[pi];
+  if (bid >= G) return;
+#define STONK_TN_A4_BID bid
+#else
 __global__ __launch_bounds__(256, 1) void STONK_TN_A4_KERNEL(const GemmArgs p) {
+#define STONK_TN_A4_BID blockIdx.x
+#endif
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -83,7 +111,9 @@ __global__ __launch_bounds__(256, 1) void STONK_TN_A4_KERNEL(const GemmArgs p) {
   nk_per += nk_per & 1;
   const int per_split = ntm * ntn;
   const int total = per_split * p.split_k;
+#if !STONK_TN_A4_GROUP
   const int G = gridDim.x;
+#endif
 #if STONK_TN_A4_STORE
   if (nk_total == 0) {   // (one K split: every work item is empty) each output tile is defined as zeros, row by row
     const int ldc0 = (int)p.ldc;
@@ -169,7 +199,7 @@ __global__ __launch_bounds__(256, 1) void STONK_TN_A4_KERNEL(const GemmArgs p) {
   };
 
   Work cw, nw;
-  int cwi = blockIdx.x;
+  int cwi = STONK_TN_A4_BID;
   if (!get_work(cwi, cw)) return;
   if (cw.nk <= 0 && !next_live_work(get_work, cwi, G, cw)) return;   // (k_dev may leave a K split empty)
   Cursor ca, cb;
@@ -316,10 +346,17 @@ __global__ __launch_bounds__(256, 1) void STONK_TN_A4_KERNEL(const GemmArgs p) {
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #undef STONK_TN_A4_DMA_OPERANDS
+#undef STONK_TN_A4_BID
 }
 
 }  // namespace
 
+#if STONK_TN_A4_GROUP
+// the grouped form; g.first / g.items / every split_k already chosen (stonk_gemm_tn_bf16_group), grid = blocks in all
+int STONK_TN_A4_LAUNCH(const TnGroupArgs& g, int grid, hipStream_t st) {
+  return launch_with_lds<STONK_TN_A4_KERNEL, LDS_BYTES>(g, grid, 256, st);
+}
+#else
 // weight-gradient form on the written-out loop; a.split_k already chosen, a.flags = grid cap in CUs (stonk_gemm_tn_bf16)
 int STONK_TN_A4_LAUNCH(const GemmArgs& a, hipStream_t st) {
   const int n_cu = cu_count();
@@ -329,3 +366,4 @@ int STONK_TN_A4_LAUNCH(const GemmArgs& a, hipStream_t st) {
   const int grid = (int)(tiles < cap ? tiles : cap);
   return launch_with_lds<STONK_TN_A4_KERNEL, LDS_BYTES>(a, grid, 256, st);
 }
+#endif

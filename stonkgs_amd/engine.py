@@ -227,6 +227,13 @@ class Engine:
         # and the `notify` hooks are skipped. False: every path issues exactly the launches it issued before the flag.
         self._inputs_only = False
         self.tn_cus = 160         # CU share of the side-stream weight gradients (tools/sweep_engine_int.py)
+        # Weight gradients of a layer that leave as ONE launch of the grouped kernel (stonk_gemm_tn_bf16_group), the earlier
+        # one held until the later one's operands are ready: "attn" = attention output + fused QKV, "ffn" = FFN down + FFN
+        # up. Together they fill the CU share with fewer K splits each: half the float-atomic bytes, one launch
+        # (DESIGN.md section 4.3). "attn" is 0.24 ms of the step; "ffn" measured 0.01 ms on top of it and is off
+        # (profiles/wgrad_groups.md).
+        self.wgrad_groups: frozenset = frozenset({"attn"})
+        self.group_log = collections.deque(maxlen=64)   # (members, status) of the latest grouped launches (tests, debugging)
         # roctx ranges around the blocks of SURVEY section 2.3 (K1 backbone ... K16 optimizer), so that a
         # `rocprofv3 --marker-trace --kernel-trace` timeline reads by block. Off unless STONK_ROCTX=1 (read once, here).
         self.roctx = bool(os.environ.get("STONK_ROCTX"))
@@ -408,6 +415,37 @@ class Engine:
                 dW.zero_()
                 self.grad_stale.discard(name)
             hip.call("stonk_gemm_tn_bf16", *args)
+
+    def _groupable(self, kind: str, shapes) -> bool:
+        """Whether the weight gradients `shapes` = [(M_out, N_in, T), ...] of one layer go out as ONE grouped launch
+        (stonk_gemm_tn_bf16_group) once the operands of the last are ready: the group is switched on, the launches go to the
+        second stream, the members share one row count (not the pruned last layer's attention pair) and each of them
+        is one the four-wave kernel takes today. Decided BEFORE the first member is held back, so that everything else is
+        launched exactly where it was."""
+        if kind not in self.wgrad_groups or not self.overlap_wgrad or self._inputs_only:
+            return False
+        return len({T for _, _, T in shapes}) == 1 and all(self._split_k(M, N, T, True) <= 0 for M, N, T in shapes)
+
+    def wgrad_group(self, members) -> None:
+        """`wgrad` for members = [(dy, x, dW, db, M_out, N_in, T), ...] that `_groupable` admitted, as one launch on the
+        second stream, ordered after everything enqueued so far on the current one: every member's operands must be
+        complete by now and must stay as they are until the side stream is done with them (the caller's business). A
+        GemmTimer sees one launch with the members' summed FLOPs. A group the library refuses for its shape goes out as
+        single launches, here. (Members carry no store-mode name - the layers' gradients have none - so `grad_stale`,
+        `sumsq_valid` and `store_log` have nothing to record; a named gradient goes through `wgrad`.)"""
+        T = members[0][6]
+        probs = hip.tn_problems([(dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), dW.data_ptr(), dW.stride(0), hip.ptr(db),
+                                  M, N, T, 1.0, 0) for dy, x, dW, db, M, N, T in members])
+        with self._fork("_wstream"), self._timed("tn_a4", sum(m[4] * m[5] for m in members), 1, T):
+            rc = hip.lib().stonk_gemm_tn_bf16_group(probs, len(members), self.tn_cus, hip.stream_ptr())
+        self.group_log.append((len(members), rc))
+        if rc == hip.ESHAPE:
+            if self.gemm_timer is not None:
+                self.gemm_timer.records.pop()   # (nothing ran between its two events)
+            for m in members:
+                self.wgrad(*m)
+            return
+        hip.check(rc, "stonk_gemm_tn_bf16_group")
 
     def _sumsq_slots(self, name, M, N, K, split) -> Optional[torch.Tensor]:
         """The region of the slot buffer that the store launch of weight `name` fills (one float per output tile), or None
@@ -647,13 +685,22 @@ class Engine:
         if df is None:
             df = ds2
         # ---- FFN down: wgrad, bias grad, dgrad fused with GELU'
-        self.wgrad(df, sv["g"], g_(prefix + ".output.dense.weight"), g_(prefix + ".output.dense.bias"), H, I, Tf)
+        # (a held weight gradient: its operands - df / da of this parity, a saved activation - are written by nothing else in
+        # this layer, and the next writer of this parity's buffers, layer i-2, first waits for `_wgrad_done[par]`, which is
+        # recorded behind the grouped launch below)
+        w_down = (df, sv["g"], g_(prefix + ".output.dense.weight"), g_(prefix + ".output.dense.bias"), H, I, Tf)
+        group_ffn = self._groupable("ffn", [(H, I, Tf), (I, H, Tf)])
+        if not group_ffn:
+            self.wgrad(*w_down)
         du = self.buf(f"b.du.{par}", (cap, I))
         self.gemm(df, wt[prefix + ".output.dense.weight"], du, Tf, I, H, flags=hip.EPI_GELU_BWD | hip.EPI_AUX_GRAD,
                   aux=sv["u"], kernel=self._kernel("dgrad_gelu", True))
         # ---- FFN up
-        self.wgrad(du, sv["h1"], g_(prefix + ".intermediate.dense.weight"), g_(prefix + ".intermediate.dense.bias"), I, H,
-                   Tf)
+        w_up = (du, sv["h1"], g_(prefix + ".intermediate.dense.weight"), g_(prefix + ".intermediate.dense.bias"), I, H, Tf)
+        if group_ffn:
+            self.wgrad_group([w_down, w_up])
+        else:
+            self.wgrad(*w_up)
         qattn = rd is not None and rd.attn
         Ta = Tf if qattn else T                    # rows the attention block's projection / LayerNorm ran on
         dh1 = self.buf("b.dh1", (cap, H))
@@ -672,8 +719,11 @@ class Engine:
         if da is None:
             da = ds1
         # ---- attention output projection
-        self.wgrad(da, sv["ctx_in"], g_(prefix + ".attention.output.dense.weight"),
-                   g_(prefix + ".attention.output.dense.bias"), H, H, Ta)
+        w_out = (da, sv["ctx_in"], g_(prefix + ".attention.output.dense.weight"),
+                 g_(prefix + ".attention.output.dense.bias"), H, H, Ta)
+        group_attn = self._groupable("attn", [(3 * H, H, T), (H, H, Ta)])
+        if not group_attn:
+            self.wgrad(*w_out)
         dctx = self.buf("b.dctx", (cap, H))
         dctxa = self.buf("b.dctxrd", (cap, H)) if qattn else dctx
         self.gemm(da, wt[prefix + ".attention.output.dense.weight"], dctxa, Ta, H, H,
@@ -699,8 +749,11 @@ class Engine:
                  1.0 / math.sqrt(64.0), p_att, self.seed(lidx, 1))
         hip.call("stonk_attention_bwd", *aargs, st)
         # ---- QKV projection
-        self.wgrad(dqkv, sv["x"], g_(prefix + ".attention.self.qkv.weight"), g_(prefix + ".attention.self.qkv.bias"),
-                   3 * H, H, T)
+        w_qkv = (dqkv, sv["x"], g_(prefix + ".attention.self.qkv.weight"), g_(prefix + ".attention.self.qkv.bias"), 3 * H, H, T)
+        if group_attn:
+            self.wgrad_group([w_qkv, w_out])
+        else:
+            self.wgrad(*w_qkv)
         dx = self.buf(f"b.dx{lidx & 1}", (cap, H))
         self.gemm(dqkv, wt[prefix + ".attention.self.qkv.weight"], dx, T, H, 3 * H, flags=hip.EPI_RESID, resid=ds1,
                   kernel=self._kernel("dgrad_resid", True))
