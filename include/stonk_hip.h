@@ -146,6 +146,29 @@ int stonk_text_embed_ln_fwd(const int64_t* input_ids, int64_t ld_ids, const floa
 int stonk_embed_grad(const void* dx, const int64_t* token_type_ids, float* dpos, float* dtype, int B, int S, int H,
                      int type_rows, const int* row_of_pos, void* stream);
 
+/* BigBird's embeddings on given inputs_embeds: y = LayerNorm(dropout(inputs_embeds + token_type + position)) - the dropout
+ * BEFORE the LayerNorm (BERT's order is the opposite). Replaces hf:models/big_bird/modeling_big_bird.py BigBirdEmbeddings
+ * :120-128 with inputs_embeds given and rescale_embeddings off. inputs_embeds fp32 [B*S, ld_in]; token_type_ids int64 [B,S]
+ * or NULL (every position type 0; the launcher has no error word: an id outside [0, type_rows) reads row 0, the caller
+ * checks); pos_emb fp32 [>= S, H], type_emb fp32 [type_rows, H]. sum_out bf16 [B*S, H]: the LayerNorm's input AFTER the
+ * dropout (what stonk_layernorm_bwd takes as x); y bf16 [B*S, H]; mean / rstd fp32 [B*S], from the fp32 values. The mask is
+ * the element form of the generator at (row, column) = (output row, column), scale 1 / (1 - drop_p), as at the
+ * STONK_LN_DROPOUT site; drop_p == 0 keeps everything.
+ * Refused: a null pointer other than token_type_ids, drop_p outside [0, 1) (STONK_EINVAL); B < 0, S <= 0, H <= 0, H % 8,
+ * H > 1024, ld_in < H, type_rows <= 0, B * S >= 2^31 (STONK_ESHAPE); ld_in % 4, inputs_embeds / pos_emb / type_emb / gamma /
+ * beta / sum_out / y not 16-byte aligned (STONK_EALIGN). B == 0 returns STONK_OK. */
+int stonk_embeds_ln_fwd(const float* inputs_embeds, int64_t ld_in, const int64_t* token_type_ids, const float* pos_emb,
+                        const float* type_emb, const float* gamma, const float* beta, void* sum_out, void* y, float* mean,
+                        float* rstd, int B, int S, int H, int type_rows, float eps, float drop_p, uint32_t seed, void* stream);
+/* The end of its backward (the backward of :127, nn.Dropout, and of the two adds): dsum bf16 [n_rows, ld] = d(sum_out) from
+ * stonk_layernorm_bwd; the mask of (drop_p, seed) is regenerated and g = keep ? dsum / (1 - drop_p) : 0 is written twice:
+ * d_inputs_embeds fp32 [n_rows, ld_out] and dx_masked bf16 [n_rows, H], which stonk_embed_grad turns into the position and
+ * token-type gradients. Refused: a null pointer, drop_p outside [0, 1) (STONK_EINVAL); n_rows < 0 or >= 2^31, H <= 0, H % 8,
+ * H > 1024, ld < H, ld_out < H (STONK_ESHAPE); ld % 8, ld_out % 4, a pointer not 16-byte aligned (STONK_EALIGN).
+ * n_rows == 0 returns STONK_OK. */
+int stonk_embeds_ln_bwd_finish(const void* dsum, int64_t ld, float* d_inputs_embeds, int64_t ld_out, void* dx_masked,
+                               int64_t n_rows, int H, float drop_p, uint32_t seed, void* stream);
+
 /* Gradient of a TRAINABLE word-embedding lookup (csrc/text_embed.hip): the text-only BERT of
  * ref:src/stonkgs/models/nlp_baseline_model.py:171-173 trains `bert.embeddings.word_embeddings.weight`, which STonKGs
  * leaves dead. Replaces the backward of nn.Embedding(V, H, padding_idx) in BertEmbeddings, hf:models/bert/modeling_bert.py:98-108
@@ -277,6 +300,28 @@ int stonk_block_sparse_attention_bwd(const void* q, const void* k, const void* v
                                      const void* dout, int64_t lddo, const float* lse, float* delta_ws, void* dq, void* dk,
                                      int64_t ldd, void* dv, int B, int NH, int S, int D, float scale, int* err_flag,
                                      void* stream);
+/* The two entries above with `flags` (the entries above ARE these with flags = 0, bit for bit). One flag,
+ * STONK_BSA_ZERO_MASKED_QUERIES: HuggingFace's rule for a masked QUERY. Replaces `context_layer = context_layer * from_mask`,
+ * hf:models/big_bird/modeling_big_bird.py:617, and its backward - with the flag these entries replace :295-744 on EVERY row.
+ * With the flag and a non-null attention_mask, for a position whose own mask word is 0:
+ *   forward   its `out` row is exact zeros for every head (its lse entry is written as without the flag, finite);
+ *   backward  its dout counts as zero: its dq row is exact zeros, it adds nothing to any dk / dv, its delta (delta_ws) is 0;
+ *             a live row's dq is the flag-less run's, bit for bit.
+ * A sequence without any live key therefore gets all-zero out, dq, dk and dv. The mask word is applied inside the kernels
+ * (on the packed bits of the forward's final store; to delta and to the dO fragments and tiles in the backward, whose
+ * arithmetic then yields the zeros by itself): no extra pass over [B*S, H], no atomics, bitwise repeatable. With a null attention_mask the flag changes nothing.
+ * Refused as the entries above, plus: a bit of `flags` other than STONK_BSA_ZERO_MASKED_QUERIES (STONK_EINVAL).
+ * B == 0 returns STONK_OK. */
+int stonk_block_sparse_attention_fwd_ex(const void* q, const void* k, const void* v, int64_t ld, const int64_t* attention_mask,
+                                        const int* key_blocks, const int* key_mult, const int* key_count, void* out,
+                                        int64_t ldo, float* lse, int B, int NH, int S, int D, float scale, int* err_flag,
+                                        int flags, void* stream);
+int stonk_block_sparse_attention_bwd_ex(const void* q, const void* k, const void* v, int64_t ld, const int64_t* attention_mask,
+                                        const int* key_blocks, const int* key_mult, const int* key_count,
+                                        const int* query_blocks, const int* query_mult, const int* query_count, const void* out,
+                                        int64_t ldo, const void* dout, int64_t lddo, const float* lse, float* delta_ws, void* dq,
+                                        void* dk, int64_t ldd, void* dv, int B, int NH, int S, int D, float scale,
+                                        int* err_flag, int flags, void* stream);
 
 /* P = softmax(q k^T * scale + key mask), written out. Forward-only, no dropout, PADDED layout only (csrc/attention_probs.hip).
  * q/k: column slices of the [B*S, 3H] projection (row stride ld), head h at columns h*64.. ; attention_mask int64 [B,S]
@@ -408,6 +453,18 @@ int stonk_elementwise_loss_fwd_bwd(const float* logits, const float* targets, in
 
 /* du = dg * gelu'(u), bf16 elementwise (backward of hf:modeling_bert.py:478, the head transform's activation). */
 int stonk_gelu_bwd_bf16(const void* dg, const void* u, void* du, int64_t n, void* stream);
+
+/* gelu_new, BigBird's hidden_act (csrc/bigbird_rowwise.hip), bf16 elementwise, fp32 arithmetic, 16-byte vectors:
+ *   g  = 0.5 u (1 + tanh(c (u + 0.044715 u^3))),  c = sqrt(2 / pi)
+ *   du = dg [0.5 (1 + t) + 0.5 u (1 - t^2) c (1 + 3 * 0.044715 u^2)]
+ * Replaces hf:activations.py NewGELUActivation as BigBirdIntermediate applies it (hf:models/big_bird/modeling_big_bird.py
+ * BigBirdIntermediate.forward) and its backward: the GEMM epilogues carry the erf form only, so the BigBird encoder's FFN-up
+ * GEMM runs with STONK_EPI_BIAS, writes the bf16 pre-activation u, and these follow (backward: the plain dgrad GEMM, then
+ * _bwd, which may run in place, du == dg). Finite for EVERY finite bf16 u, +-bf16-max included: the derivative's second term
+ * is dropped once |2 c (u + 0.044715 u^3)| >= 87, where 1 - t^2 < 4e-38 and u (1 + 3 k u^2) may overflow.
+ * Refused: a null pointer, n < 0, n % 8 (STONK_EINVAL); a pointer not 16-byte aligned (STONK_EALIGN). n == 0 returns STONK_OK. */
+int stonk_gelu_new_fwd_bf16(const void* u, void* g, int64_t n, void* stream);
+int stonk_gelu_new_bwd_bf16(const void* dg, const void* u, void* du, int64_t n, void* stream);
 
 /* Optimizer step pieces (hf:trainer.py:1780-1796 as driven by ref:src/stonkgs/models/stonkgs_pretraining.py:171-223):
  * *out_accum += sum(x^2), summed in a fixed order (bitwise repeatable: data-parallel replicas rely on it) through a caller

@@ -34,6 +34,7 @@ SMALL_X_F32 = 16
 LOSS_MSE, LOSS_MSE_BROADCAST, LOSS_BCE = 0, 1, 2
 OK, EINVAL, ESHAPE, EALIGN = 0, -1, -2, -3   # launcher status codes (include/stonk_hip.h)
 ATTN_BWD_DELTA, ATTN_BWD_DQ, ATTN_BWD_DKV, ATTN_BWD_ALL = 1, 2, 4, 7
+BSA_ZERO_MASKED_QUERIES = 1 << 0   # stonk_block_sparse_attention_*_ex `flags`: HuggingFace's context * from_mask
 
 _vp, _i32, _i64, _f32, _u32, _f64 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint32, C.c_double
 
@@ -67,6 +68,16 @@ _SIGNATURES = {
                                          _vp, _vp],
     "stonk_block_sparse_attention_bwd": [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp,
                                          _vp, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp],
+    "stonk_block_sparse_attention_fwd_ex": [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _f32,
+                                            _vp, _i32, _vp],   # ... err_flag, flags (BSA_*), stream
+    "stonk_block_sparse_attention_bwd_ex": [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp,
+                                            _vp, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _i32, _vp],
+    # the BigBird encoder's row-wise kernels: gelu_new, embeddings on inputs_embeds (csrc/bigbird_rowwise.hip)
+    "stonk_gelu_new_fwd_bf16": [_vp, _vp, _i64, _vp],
+    "stonk_gelu_new_bwd_bf16": [_vp, _vp, _vp, _i64, _vp],
+    "stonk_embeds_ln_fwd": [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _f32, _u32,
+                            _vp],
+    "stonk_embeds_ln_bwd_finish": [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _f32, _u32, _vp],
     "stonk_attention_probs": [_vp, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp],
     "stonk_transpose_bf16": [_vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp],
     "stonk_transpose_f32_to_bf16": [_vp, _vp, _i64, _i32, _i64, _vp],

@@ -163,7 +163,7 @@ class BlockSparsePlan:
 
 class _BlockSparseAttention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, attention_mask, plan, num_heads, scale):
+    def forward(ctx, qkv, attention_mask, plan, num_heads, scale, flags):
         H = num_heads * BLOCK
         S = plan.num_blocks * BLOCK
         if not qkv.is_cuda:
@@ -183,14 +183,14 @@ class _BlockSparseAttention(torch.autograd.Function):
         out = torch.empty(B * S, H, device=qkv.device, dtype=torch.bfloat16)
         lse = torch.empty(B, num_heads, S, device=qkv.device, dtype=torch.float32)
         p = hip.ptr(qkv)
-        hip.call("stonk_block_sparse_attention_fwd", p, p + 2 * H, p + 4 * H, 3 * H, hip.ptr(attention_mask),
+        hip.call("stonk_block_sparse_attention_fwd_ex", p, p + 2 * H, p + 4 * H, 3 * H, hip.ptr(attention_mask),
                  *(hip.ptr(t) for t in lists[:3]), hip.ptr(out), H, hip.ptr(lse), B, num_heads, S, BLOCK, scale, hip.ptr(err),
-                 hip.stream_ptr())
+                 flags, hip.stream_ptr())
         if int(err.item()):
             err.zero_()
             raise IndexError("block_sparse_attention: a list entry, multiplicity or count of the plan is out of range")
         ctx.save_for_backward(qkv, attention_mask, out, lse)
-        ctx.plan, ctx.num_heads, ctx.scale = plan, num_heads, scale
+        ctx.plan, ctx.num_heads, ctx.scale, ctx.flags = plan, num_heads, scale, flags
         return out
 
     @staticmethod
@@ -204,36 +204,46 @@ class _BlockSparseAttention(torch.autograd.Function):
         dqkv = torch.empty_like(qkv)
         ws = torch.empty(2, B, num_heads, S, device=qkv.device, dtype=torch.float32)
         p, g = hip.ptr(qkv), hip.ptr(dqkv)
-        hip.call("stonk_block_sparse_attention_bwd", p, p + 2 * H, p + 4 * H, 3 * H, hip.ptr(attention_mask),
+        hip.call("stonk_block_sparse_attention_bwd_ex", p, p + 2 * H, p + 4 * H, 3 * H, hip.ptr(attention_mask),
                  *(hip.ptr(t) for t in lists), hip.ptr(out), H, hip.ptr(dout), H, hip.ptr(lse), hip.ptr(ws), g, g + 2 * H, 3 * H,
-                 g + 4 * H, B, num_heads, S, BLOCK, scale, hip.ptr(err), hip.stream_ptr())
-        return dqkv, None, None, None, None
+                 g + 4 * H, B, num_heads, S, BLOCK, scale, hip.ptr(err), ctx.flags, hip.stream_ptr())
+        return dqkv, None, None, None, None, None
 
 
-def block_sparse_attention(qkv, attention_mask, plan, num_heads, scale=None):
+def block_sparse_attention(qkv, attention_mask, plan, num_heads, scale=None, zero_masked_queries=False):
     """softmax over the plan's listed key blocks (with multiplicities) . V, per head.
+
+    zero_masked_queries: HuggingFace's ``context_layer * from_mask`` (modeling_big_bird.py:617) - the output row of a
+    position whose own mask word is 0 is exact zeros and no gradient passes through it (STONK_BSA_ZERO_MASKED_QUERIES, applied
+    inside the kernels). Off, such a row is the list formulation's row.
 
     qkv: bf16 [B*S, 3H] contiguous (q | k | v, head h at columns h*64..), S = 64 * plan.num_blocks; attention_mask int64
     [B, S] (0 = masked key) or None; returns bf16 [B*S, H]. Differentiable with respect to qkv. Raises IndexError when the
     kernels find a list entry out of range (one device-to-host word per call, as Engine.check_errors reads)."""
     if scale is None:
         scale = 1.0 / math.sqrt(BLOCK)
-    return _BlockSparseAttention.apply(qkv, attention_mask, plan, int(num_heads), float(scale))
+    flags = hip.BSA_ZERO_MASKED_QUERIES if zero_masked_queries else 0
+    return _BlockSparseAttention.apply(qkv, attention_mask, plan, int(num_heads), float(scale), flags)
 
 
 class BigBirdBlockSparseSelfAttention(nn.Module):
-    """Drop-in for HuggingFace's BigBirdBlockSparseAttention (block size 64, head dimension 64): the same ``query`` / ``key`` /
-    ``value`` linears, so ``load_state_dict`` takes its state dict unchanged. The projections run in torch in bf16; the
+    """Stands in for HuggingFace's BigBirdBlockSparseAttention (block size 64, head dimension 64): the same ``query`` / ``key`` /
+    ``value`` linears, so ``load_state_dict`` takes its state dict unchanged. What "drop-in" means depends on
+    ``zero_masked_queries``: True, every row is HuggingFace's - the context row of a position whose own mask word is 0 is exact
+    zeros (its ``context_layer * from_mask``, :617) and takes no gradient; False (the default), only the rows whose own mask
+    word is 1 are HuggingFace's, and a masked position's row is the list formulation's row (its block's softmax over the live
+    listed keys), which HuggingFace never returns. The projections run in torch in bf16; the
     attention is block_sparse_attention. ``.eval()`` uses the zeros plan, ``.train()`` a plan drawn once per module from
     ``layer_seed`` (HuggingFace's is fixed per layer by its seed as well, but from another random stream). No dropout and no
     attention-probability output."""
 
-    def __init__(self, hidden_size, num_heads, num_random_blocks=3, layer_seed=0):
+    def __init__(self, hidden_size, num_heads, num_random_blocks=3, layer_seed=0, zero_masked_queries=False):
         super().__init__()
         if hidden_size != num_heads * BLOCK:
             raise ValueError(f"hidden_size must be num_heads * {BLOCK}: the kernels are built for head dimension {BLOCK}")
         self.hidden_size, self.num_heads = int(hidden_size), int(num_heads)
         self.num_random_blocks, self.layer_seed = int(num_random_blocks), int(layer_seed)
+        self.zero_masked_queries = bool(zero_masked_queries)
         self.query = nn.Linear(hidden_size, hidden_size, bias=True)
         self.key = nn.Linear(hidden_size, hidden_size, bias=True)
         self.value = nn.Linear(hidden_size, hidden_size, bias=True)
@@ -260,5 +270,6 @@ class BigBirdBlockSparseSelfAttention(nn.Module):
         if H != self.hidden_size or S % BLOCK:
             raise ValueError(f"hidden_states must be [B, S, {self.hidden_size}] with S a multiple of {BLOCK}, got {tuple(hidden_states.shape)}")
         hip.lib()   # (raises if the library has not been built)
-        ctx = block_sparse_attention(self.project(hidden_states), attention_mask, self.plan_for(S // BLOCK), self.num_heads)
+        ctx = block_sparse_attention(self.project(hidden_states), attention_mask, self.plan_for(S // BLOCK), self.num_heads,
+                                     zero_masked_queries=self.zero_masked_queries)
         return ctx.view(B, S, H).to(hidden_states.dtype)

@@ -26,8 +26,19 @@
 // The lists live in device memory, where the launcher cannot check them: a count outside [0, nb] (the list then counts as
 // empty), an entry outside [0, nb) or a multiplicity <= 0 (the entry is skipped) sets bit 0 of *err_flag and reads nothing
 // through the bad value. A block with no valid entry writes zeros.
+//
+// STONK_BSA_ZERO_MASKED_QUERIES (the _ex entries, with a mask): HuggingFace ends with context_layer * from_mask (:617), so
+// the context row of a query whose OWN mask word is 0 is exactly zero and no gradient passes through it. The kernels' ZQ
+// instances apply the row's mask word where the row leaves or enters them: the forward at its final store (the lse is
+// written as without the flag), bb_prep to delta, bb_bwd_dq to its dO fragment and delta, bb_bwd_dkv to the
+// rows of every dO tile as it is staged (delta arrives zeroed from bb_prep) - a masked row then has dP = 0 and delta = 0,
+// hence dS = P (0 - 0) = 0 and P^T dO = 0 exactly: nothing reaches dK / dV, and no pass over [B*S, H] is added. The
+// instances without ZQ are the kernels as they were. The ZQ instances are compiled in a translation unit of their own,
+// bigbird_attention_zq.hip, which includes this file with STONK_BB_ZQ_UNIT defined (as gemm_tn_a4_store.hip includes
+// gemm_tn_a4.hip): this object keeps the kernels it had, and the two objects meet in stonk_bb::launch_zq_*.
 #include "common.h"
 #include "attn_tiles.h"
+#include "stonk_flags.h"
 
 namespace {
 
@@ -59,6 +70,7 @@ struct BbArgs {
   int B, NH, S, nb;
   float scale;
   int* err;
+  int zq;             // bb_prep: delta = 0 for a row whose mask word is 0 (the other kernels take ZQ as a template argument)
 };
 
 // Workgroup -> (block, head, sequence). The 2 B NH workgroups of blocks 0 and nb-1 - nb tiles each, against 5 to 8 - take
@@ -127,7 +139,7 @@ __device__ __forceinline__ int bb_list(const int* blocks, const int* mult, const
 __device__ __forceinline__ bool bb_degenerate(float lse, float scale) { return lse < 0.5f * NEG_MASK * scale; }
 
 // ------------------------------------------------------------------ forward
-template <bool HAS_MASK>
+template <bool HAS_MASK, bool ZQ>
 __global__ __launch_bounds__(256, 2) void bb_fwd_kernel(const BbArgs p) {
   __shared__ __attribute__((aligned(16))) char lds[BB_LDS];
   int* lj = (int*)(lds + 2 * STAGEB);
@@ -241,6 +253,8 @@ __global__ __launch_bounds__(256, 2) void bb_fwd_kernel(const BbArgs p) {
   const float a0 = __builtin_amdgcn_exp2f(m - mf), a1 = __builtin_amdgcn_exp2f(m1 - mf);
   l = l * a0 + l1 * a1;
   const float inv = l > 0.f ? 1.f / l : 0.f;   // (l == 0: a block without a valid list entry writes zeros)
+  unsigned long live_bits = ~0ul;   // ZQ: all ones for a live query, zero for a masked one (the row's own mask word)
+  if (ZQ) live_bits = p.mask[tok0 + q0 + r] != 0 ? ~0ul : 0ul;
   bf16* orow = p.out + (tok0 + q0 + r) * p.ldo + h * HD;
 #pragma unroll
   for (int dt = 0; dt < 2; ++dt)
@@ -250,6 +264,9 @@ __global__ __launch_bounds__(256, 2) void bb_fwd_kernel(const BbArgs p) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) e[j] = (o[dt][4 * g + j] * a0 + xw[(2 + dt * 16 + 4 * g + j) * 64] * a1) * inv;
       bf16x4 v = {(bf16)e[0], (bf16)e[1], (bf16)e[2], (bf16)e[3]};
+      // (the mask word goes onto the packed BITS: a select on the floats changes how the compiler vectorises and contracts the
+      // line above, and a live row's last bit with it - the flag must not be visible in a live row)
+      if (ZQ) v = __builtin_bit_cast(bf16x4, __builtin_bit_cast(unsigned long, v) & live_bits);
       *(bf16x4*)(orow + dt * 32 + 8 * g + 4 * hh) = v;
     }
   if (hh == 0) p.lse[(long)(b * p.NH + h) * S + q0 + r] = l > 0.f ? (mf + __builtin_amdgcn_logf(l)) * LN2 : 0.f;
@@ -258,6 +275,7 @@ __global__ __launch_bounds__(256, 2) void bb_fwd_kernel(const BbArgs p) {
 // ------------------------------------------------------------------ backward: per-row statistics
 // delta = rowsum(dO * O) (delta_row: the one summation order of every producer of delta) and -lse in log2 units - for a row whose listed keys
 // are all masked -log2(64 L) instead, L = the total multiplicity of its block's list (see the head of the file).
+#ifndef STONK_BB_ZQ_UNIT
 __global__ __launch_bounds__(128) void bb_prep_kernel(const BbArgs p) {
   const long rows = (long)p.B * p.NH * p.S;
   const long idx = (long)blockIdx.x * 128 + threadIdx.x;
@@ -267,7 +285,9 @@ __global__ __launch_bounds__(128) void bb_prep_kernel(const BbArgs p) {
   const long bh = idx / S;
   const int h = (int)(bh % p.NH);
   const long tok = (bh / p.NH) * S + qrow;
-  p.ws[idx] = delta_row(p.dout + tok * p.lddo + h * HD, p.out + tok * p.ldo + h * HD);
+  float delta = delta_row(p.dout + tok * p.lddo + h * HD, p.out + tok * p.ldo + h * HD);
+  if (p.zq && p.mask[tok] == 0) delta = 0.f;   // (a masked query's dO counts as zero)
+  p.ws[idx] = delta;
   const float lse = p.lse[idx];
   float nls = -lse * LOG2E;
   if (bb_degenerate(lse, p.scale)) {
@@ -283,9 +303,10 @@ __global__ __launch_bounds__(128) void bb_prep_kernel(const BbArgs p) {
   }
   p.ws[rows + idx] = nls;
 }
+#endif
 
 // ------------------------------------------------------------------ backward: dQ (query on the lane)
-template <bool HAS_MASK>
+template <bool HAS_MASK, bool ZQ>
 __global__ __launch_bounds__(256, 2) void bb_bwd_dq_kernel(const BbArgs p) {
   __shared__ __attribute__((aligned(16))) char lds[BB_LDS];
   int* lj = (int*)(lds + 2 * STAGEB);
@@ -313,7 +334,16 @@ __global__ __launch_bounds__(256, 2) void bb_bwd_dq_kernel(const BbArgs p) {
   }
   const long stat = (long)(b * p.NH + h) * S + q0 + r;
   const long rows = (long)p.B * p.NH * S;
-  const float dlt = p.ws[stat], nlse2 = p.ws[rows + stat];
+  float dlt = p.ws[stat];
+  const float nlse2 = p.ws[rows + stat];
+  if (ZQ) {   // a masked query: dO and delta count as zero, so dS = m P (0 - 0) is +0 for every key (P is finite) and the
+              // accumulators stay +0: the row is stored as exact zeros by the lines every row takes
+    if (p.mask[tok0 + q0 + r] == 0) {
+      dlt = 0.f;
+#pragma unroll
+      for (int st = 0; st < 4; ++st) dof[st] = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
+    }
+  }
   const float sc2 = bb_degenerate(p.lse[stat], p.scale) ? 0.f : p.scale * LOG2E;   // (a zero score scale: P = 2^nlse2 for every key)
   f32x16 dq[2] = {zero16(), zero16()};
 
@@ -386,7 +416,7 @@ __global__ __launch_bounds__(256, 2) void bb_bwd_dq_kernel(const BbArgs p) {
 // ------------------------------------------------------------------ backward: dK, dV (key on the lane)
 // Workgroup = key block j; the tile loop walks the INVERSE list of (head, j): the query blocks that list j, with the
 // multiplicity they list it with. Waves: (32-key half) x (32-row half of every query tile).
-template <bool HAS_MASK>
+template <bool HAS_MASK, bool ZQ>
 __global__ __launch_bounds__(256, 2) void bb_bwd_dkv_kernel(const BbArgs p) {
   __shared__ __attribute__((aligned(16))) char lds[BB_LDS];
   int* lj = (int*)(lds + 2 * STAGEB);
@@ -431,15 +461,25 @@ __global__ __launch_bounds__(256, 2) void bb_bwd_dkv_kernel(const BbArgs p) {
   float lse_nx = 0.f;   // the lse of the first row of the tile in flight: whether its block is a degenerate one
   const float* sptr = tid < TK ? p.ws + rows + statbase + tid : p.ws + statbase + (tid & (TK - 1));
   const TileOff voq = tile_voff(p.ld, tid), vod = tile_voff(p.lddo, tid);
+  long qm[2] = {1, 1};   // ZQ: the mask words of the two query rows whose dO chunks this thread stages (tid / 8, + 32)
   auto load_tile = [&](int i) {
     stage_load(sq, qbase, p.ld, i * TK, S, voq);
     stage_load(sd, dbase, p.lddo, i * TK, S, vod);
+    if (ZQ) {
+      qm[0] = p.mask[tok0 + i * TK + (tid >> 3)];
+      qm[1] = p.mask[tok0 + i * TK + 32 + (tid >> 3)];
+    }
     if (tid < 2 * TK) sreg = sptr[i * TK];
     lse_nx = p.lse[statbase + i * TK];
   };
   auto store_tile = [&](int buf) {
     char* base = lds + buf * STAGEB;
     stage_store(sq, base, tid);
+    if (ZQ) {   // a masked query's dO row is staged as zeros (its delta is zero in the workspace: bb_prep)
+#pragma unroll
+      for (int c = 0; c < 2; ++c)
+        if (qm[c] == 0) sd.c[c] = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
+    }
     stage_store(sd, base + TILEB, tid);
     if (tid < 2 * TK) ((float*)(base + 2 * TILEB))[tid] = tid < TK ? sreg : -sreg;
   };
@@ -554,6 +594,23 @@ __global__ __launch_bounds__(256, 2) void bb_bwd_dkv_kernel(const BbArgs p) {
 
 static_assert(2 * 64 * 64 * 4 <= 2 * STAGEB, "the dK/dV partial sums fit the two stages");
 
+#ifdef STONK_BB_ZQ_UNIT
+}  // namespace
+
+// The ZQ instances' launches, called from bigbird_attention.hip's _ex entries (which have checked every argument): `args` is
+// that unit's BbArgs - the same struct, compiled from the same text.
+namespace stonk_bb {
+void launch_zq_fwd(const void* args, unsigned grid, void* stream) {
+  const BbArgs a = *(const BbArgs*)args;
+  hipLaunchKernelGGL((bb_fwd_kernel<true, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+}
+void launch_zq_bwd(const void* args, unsigned grid, void* stream) {
+  const BbArgs a = *(const BbArgs*)args;
+  hipLaunchKernelGGL((bb_bwd_dq_kernel<true, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL((bb_bwd_dkv_kernel<true, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+}
+}  // namespace stonk_bb
+#else
 int bb_check_common(const void* q, const void* k, const void* v, int64_t ld, const int* blocks, const int* mult,
                     const int* count, int* err_flag, int B, int NH, int S, int D, float scale) {
   STONK_CHECK_ARG(q && k && v && blocks && mult && count && err_flag, STONK_EINVAL);
@@ -582,10 +639,17 @@ BbArgs bb_args(const void* q, const void* k, const void* v, int64_t ld, const in
 
 }  // namespace
 
-extern "C" int stonk_block_sparse_attention_fwd(const void* q, const void* k, const void* v, int64_t ld,
-                                                const int64_t* attention_mask, const int* key_blocks, const int* key_mult,
-                                                const int* key_count, void* out, int64_t ldo, float* lse, int B, int NH,
-                                                int S, int D, float scale, int* err_flag, void* stream) {
+namespace stonk_bb {   // bigbird_attention_zq.hip
+void launch_zq_fwd(const void* args, unsigned grid, void* stream);
+void launch_zq_bwd(const void* args, unsigned grid, void* stream);
+}  // namespace stonk_bb
+
+extern "C" int stonk_block_sparse_attention_fwd_ex(const void* q, const void* k, const void* v, int64_t ld,
+                                                   const int64_t* attention_mask, const int* key_blocks,
+                                                   const int* key_mult, const int* key_count, void* out, int64_t ldo,
+                                                   float* lse, int B, int NH, int S, int D, float scale, int* err_flag,
+                                                   int flags, void* stream) {
+  STONK_CHECK_ARG((flags & ~STONK_BSA_ZERO_MASKED_QUERIES) == 0, STONK_EINVAL);
   int rc = bb_check_common(q, k, v, ld, key_blocks, key_mult, key_count, err_flag, B, NH, S, D, scale);
   if (rc) return rc;
   STONK_CHECK_ARG(out && lse, STONK_EINVAL);
@@ -595,17 +659,28 @@ extern "C" int stonk_block_sparse_attention_fwd(const void* q, const void* k, co
   const BbArgs a = bb_args(q, k, v, ld, attention_mask, key_blocks, key_mult, key_count, out, ldo, lse, B, NH, S, scale, err_flag);
   const dim3 grid(B * NH * a.nb), block(256);
   hipStream_t st = (hipStream_t)stream;
-  with_flag(attention_mask != nullptr, [&](auto hm) { hipLaunchKernelGGL((bb_fwd_kernel<hm()>), grid, block, 0, st, a); });
+  const bool zq = (flags & STONK_BSA_ZERO_MASKED_QUERIES) && attention_mask;   // (without a mask every query is live)
+  if (zq) stonk_bb::launch_zq_fwd(&a, grid.x, stream);
+  else with_flag(attention_mask != nullptr, [&](auto hm) { hipLaunchKernelGGL((bb_fwd_kernel<hm(), false>), grid, block, 0, st, a); });
   return stonk_launch_status();
 }
 
-extern "C" int stonk_block_sparse_attention_bwd(const void* q, const void* k, const void* v, int64_t ld,
+extern "C" int stonk_block_sparse_attention_fwd(const void* q, const void* k, const void* v, int64_t ld,
                                                 const int64_t* attention_mask, const int* key_blocks, const int* key_mult,
-                                                const int* key_count, const int* query_blocks, const int* query_mult,
-                                                const int* query_count, const void* out, int64_t ldo, const void* dout,
-                                                int64_t lddo, const float* lse, float* delta_ws, void* dq, void* dk,
-                                                int64_t ldd, void* dv, int B, int NH, int S, int D, float scale,
-                                                int* err_flag, void* stream) {
+                                                const int* key_count, void* out, int64_t ldo, float* lse, int B, int NH,
+                                                int S, int D, float scale, int* err_flag, void* stream) {
+  return stonk_block_sparse_attention_fwd_ex(q, k, v, ld, attention_mask, key_blocks, key_mult, key_count, out, ldo, lse, B,
+                                             NH, S, D, scale, err_flag, 0, stream);
+}
+
+extern "C" int stonk_block_sparse_attention_bwd_ex(const void* q, const void* k, const void* v, int64_t ld,
+                                                   const int64_t* attention_mask, const int* key_blocks,
+                                                   const int* key_mult, const int* key_count, const int* query_blocks,
+                                                   const int* query_mult, const int* query_count, const void* out,
+                                                   int64_t ldo, const void* dout, int64_t lddo, const float* lse,
+                                                   float* delta_ws, void* dq, void* dk, int64_t ldd, void* dv, int B, int NH,
+                                                   int S, int D, float scale, int* err_flag, int flags, void* stream) {
+  STONK_CHECK_ARG((flags & ~STONK_BSA_ZERO_MASKED_QUERIES) == 0, STONK_EINVAL);
   int rc = bb_check_common(q, k, v, ld, key_blocks, key_mult, key_count, err_flag, B, NH, S, D, scale);
   if (rc) return rc;
   STONK_CHECK_ARG(query_blocks && query_mult && query_count && out && dout && lse && delta_ws && dq && dk && dv, STONK_EINVAL);
@@ -621,10 +696,29 @@ extern "C" int stonk_block_sparse_attention_bwd(const void* q, const void* k, co
   const dim3 grid(B * NH * a.nb), block(256);
   const long rows = (long)B * NH * S;
   hipStream_t st = (hipStream_t)stream;
+  const bool zq = (flags & STONK_BSA_ZERO_MASKED_QUERIES) && attention_mask;
+  a.zq = zq;
   hipLaunchKernelGGL(bb_prep_kernel, dim3((unsigned)((rows + 127) / 128)), dim3(128), 0, st, a);
-  with_flag(attention_mask != nullptr, [&](auto hm) {
-    hipLaunchKernelGGL((bb_bwd_dq_kernel<hm()>), grid, block, 0, st, a);
-    hipLaunchKernelGGL((bb_bwd_dkv_kernel<hm()>), grid, block, 0, st, a);
-  });
+  if (zq) {
+    stonk_bb::launch_zq_bwd(&a, grid.x, stream);
+  } else {
+    with_flag(attention_mask != nullptr, [&](auto hm) {
+      hipLaunchKernelGGL((bb_bwd_dq_kernel<hm(), false>), grid, block, 0, st, a);
+      hipLaunchKernelGGL((bb_bwd_dkv_kernel<hm(), false>), grid, block, 0, st, a);
+    });
+  }
   return stonk_launch_status();
 }
+
+extern "C" int stonk_block_sparse_attention_bwd(const void* q, const void* k, const void* v, int64_t ld,
+                                                const int64_t* attention_mask, const int* key_blocks, const int* key_mult,
+                                                const int* key_count, const int* query_blocks, const int* query_mult,
+                                                const int* query_count, const void* out, int64_t ldo, const void* dout,
+                                                int64_t lddo, const float* lse, float* delta_ws, void* dq, void* dk,
+                                                int64_t ldd, void* dv, int B, int NH, int S, int D, float scale,
+                                                int* err_flag, void* stream) {
+  return stonk_block_sparse_attention_bwd_ex(q, k, v, ld, attention_mask, key_blocks, key_mult, key_count, query_blocks,
+                                             query_mult, query_count, out, ldo, dout, lddo, lse, delta_ws, dq, dk, ldd, dv, B,
+                                             NH, S, D, scale, err_flag, 0, stream);
+}
+#endif  // STONK_BB_ZQ_UNIT

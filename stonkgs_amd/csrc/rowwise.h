@@ -136,3 +136,55 @@ __device__ __forceinline__ float wave_sum_uniform(float v) {
   const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 48));
   return (r0 + r1) + (r2 + r3);
 }
+
+// ---- LayerNorm of a row held in the chunk layout (norm.hip's generic kernels and embedding front-ends, bigbird_rowwise.hip) ----
+// two-pass (mean, then centred variance) statistics in fp32, as torch's native_layer_norm computes them
+template <int CPL>
+__device__ __forceinline__ void row_stats(const RowRegs<CPL>& r, int nch, int lane, int H, float eps, float& mean,
+                                          float& rstd) {
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < CPL; ++i)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) s += r.v[i][j];
+  mean = wave_sum(s) / (float)H;
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < CPL; ++i) {
+    const int c = lane + 64 * i;
+    if (c < nch) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float d = r.v[i][j] - mean;
+        q += d * d;
+      }
+    }
+  }
+  const float var = wave_sum(q) / (float)H;
+  rstd = rsqrtf(var + eps);
+}
+
+// y = (x - mean) * rstd * gamma + beta, optional inverted dropout on y
+template <int CPL>
+__device__ __forceinline__ void normalize_store(RowRegs<CPL>& r, int nch, int lane, float mean, float rstd,
+                                                const float* gamma, const float* beta, bf16* yrow, long row_idx, int H,
+                                                bool drop, uint32_t thr32, float dscale, uint32_t seed) {
+#pragma unroll
+  for (int i = 0; i < CPL; ++i) {
+    const int c = lane + 64 * i;
+    if (c < nch) {
+      const f32x4 g0 = *(const f32x4*)(gamma + c * 8), g1 = *(const f32x4*)(gamma + c * 8 + 4);
+      const f32x4 b0 = *(const f32x4*)(beta + c * 8), b1 = *(const f32x4*)(beta + c * 8 + 4);
+      bf16x8 o;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float g = j < 4 ? g0[j] : g1[j - 4];
+        const float b = j < 4 ? b0[j] : b1[j - 4];
+        float y = (r.v[i][j] - mean) * rstd * g + b;
+        if (drop) y = stonk_keep((uint32_t)row_idx, (uint32_t)(c * 8 + j), seed, thr32) ? y * dscale : 0.f;
+        o[j] = (bf16)y;
+      }
+      *(bf16x8*)(yrow + c * 8) = o;
+    }
+  }
+}

@@ -53,3 +53,7 @@
 #define STONK_ATTN_BWD_DQ 2    /* dQ (stores delta itself only in the ALL form) */
 #define STONK_ATTN_BWD_DKV 4   /* dK, dV (reads delta) */
 #define STONK_ATTN_BWD_ALL 7   /* = stonk_attention_bwd: dQ (producing delta), then dK / dV, on one stream */
+// --- stonk_block_sparse_attention_{fwd,bwd}_ex `flags` ---
+#define STONK_BSA_ZERO_MASKED_QUERIES (1 << 0) /* HuggingFace's context_layer * from_mask (modeling_big_bird.py:617): the \
+                                                  context row of a query whose own mask word is 0 is exact zeros, and its \
+                                                  dO counts as zero in the backward; nothing changes without a mask */

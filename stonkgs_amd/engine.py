@@ -614,9 +614,7 @@ class Engine:
         lse = self.buf(f"{tag}.lse", (B, NH, seq), F32)
         qattn = rd is not None and rd.attn   # queries = the read rows only (a sequence's first rows)
         qoff = rd.offsets if qattn else None
-        hip.call("stonk_attention_fwd", qkv.data_ptr(), qkv.data_ptr() + 2 * H, qkv.data_ptr() + 4 * H, 3 * H,
-                 hip.ptr(mask), hip.ptr(cu), hip.ptr(qoff), ctx.data_ptr(), H, lse.data_ptr(), B, NH, seq, 64,
-                 1.0 / math.sqrt(64.0), p_att, self.seed(lidx, 1), st)
+        self._attention_fwd(qkv, mask, cu, qoff, ctx, lse, B, NH, seq, p_att, lidx, st)
         Ta, a_in, res = T, ctx, x                  # rows / input / residual of the output projection
         if qattn:
             Ta = rd.T
@@ -639,9 +637,7 @@ class Engine:
             self._gather_rows(h1, rd.rows, rd.cnt, hf, cap)
         g = self.buf(f"{tag}.g", (cap, I))
         u = self.buf(f"{tag}.u", (cap, I)) if save is not None else None
-        fl = hip.EPI_BIAS | hip.EPI_GELU | ((hip.EPI_SAVE_PREACT | hip.EPI_AUX_GRAD) if save is not None else 0)
-        self.gemm(hf, w(prefix + ".intermediate.dense.weight"), g, Tf, I, H, flags=fl,
-                  bias=f(prefix + ".intermediate.dense.bias"), aux=u, kernel=self._kernel("ffn_up"))
+        self._ffn_up(S, prefix, hf, g, u, Tf)
         s2 = self.buf(f"{tag}.s2", (cap, H))
         fl = hip.EPI_BIAS | hip.EPI_RESID | (hip.EPI_DROPOUT if p_hid > 0 else 0)
         self.gemm(g, w(prefix + ".output.dense.weight"), s2, Tf, H, I, flags=fl, bias=f(prefix + ".output.dense.bias"),
@@ -654,6 +650,36 @@ class Engine:
         if save is not None:
             save[prefix] = dict(x=x, qkv=qkv, ctx=ctx, ctx_in=a_in, lse=lse, s1=s1, h1=hf, st1=st1, g=g, u=u, s2=s2, st2=st2)
         return y
+
+    # What a layer does between its GEMMs and LayerNorms, as methods: the dense attention core and the erf GELU carried by
+    # the FFN GEMMs' epilogues. A subclass with another attention family or activation (bigbird_encoder.BigBirdEngine)
+    # overrides these four and inherits the chain.
+    def _attention_fwd(self, qkv, mask, cu, qoff, ctx, lse, B, NH, seq, p_att, lidx, st) -> None:
+        H = self.cfg.hidden_size
+        hip.call("stonk_attention_fwd", qkv.data_ptr(), qkv.data_ptr() + 2 * H, qkv.data_ptr() + 4 * H, 3 * H,
+                 hip.ptr(mask), hip.ptr(cu), hip.ptr(qoff), ctx.data_ptr(), H, lse.data_ptr(), B, NH, seq, 64,
+                 1.0 / math.sqrt(64.0), p_att, self.seed(lidx, 1), st)
+
+    def _attention_bwd(self, qkv, mask, cu, qoff, ctx, dctx, lse, delta, dqkv, B, NH, seq, p_att, lidx, st) -> None:
+        H = self.cfg.hidden_size
+        aargs = (qkv.data_ptr(), qkv.data_ptr() + 2 * H, qkv.data_ptr() + 4 * H, 3 * H, hip.ptr(mask), hip.ptr(cu),
+                 hip.ptr(qoff), ctx.data_ptr(), H, dctx.data_ptr(), H, lse.data_ptr(), delta.data_ptr(),
+                 dqkv.data_ptr(), dqkv.data_ptr() + 2 * H, 3 * H, dqkv.data_ptr() + 4 * H, B, NH, seq, 64,
+                 1.0 / math.sqrt(64.0), p_att, self.seed(lidx, 1))
+        hip.call("stonk_attention_bwd", *aargs, st)
+
+    def _ffn_up(self, S: FlatStore, prefix: str, hf, g, u, Tf) -> None:
+        """g = act(hf . W^T + b); `u` (None in a forward-only pass): what the backward's `_ffn_down_dgrad` reads."""
+        H, I = self.cfg.hidden_size, self.cfg.intermediate_size
+        fl = hip.EPI_BIAS | hip.EPI_GELU | ((hip.EPI_SAVE_PREACT | hip.EPI_AUX_GRAD) if u is not None else 0)
+        self.gemm(hf, S.bf16_view(prefix + ".intermediate.dense.weight"), g, Tf, I, H, flags=fl,
+                  bias=S.view(prefix + ".intermediate.dense.bias"), aux=u, kernel=self._kernel("ffn_up"))
+
+    def _ffn_down_dgrad(self, prefix: str, df, du, u, Tf) -> None:
+        """du = (df . W_down) o act'(pre-activation), from what `_ffn_up` left in `u`."""
+        H, I = self.cfg.hidden_size, self.cfg.intermediate_size
+        self.gemm(df, self.P.wt[prefix + ".output.dense.weight"], du, Tf, I, H, flags=hip.EPI_GELU_BWD | hip.EPI_AUX_GRAD,
+                  aux=u, kernel=self._kernel("dgrad_gelu", True))
 
     def layer_bwd(self, prefix: str, dy, L: Rows, p_hid, p_att, lidx, sv, last: bool = False):
         """dy: bf16 [T,H] gradient of the layer output. Returns the gradient of the layer input. `L`, `last`: the
@@ -693,8 +719,7 @@ class Engine:
         if not group_ffn:
             self.wgrad(*w_down)
         du = self.buf(f"b.du.{par}", (cap, I))
-        self.gemm(df, wt[prefix + ".output.dense.weight"], du, Tf, I, H, flags=hip.EPI_GELU_BWD | hip.EPI_AUX_GRAD,
-                  aux=sv["u"], kernel=self._kernel("dgrad_gelu", True))
+        self._ffn_down_dgrad(prefix, df, du, sv["u"], Tf)
         # ---- FFN up
         w_up = (du, sv["h1"], g_(prefix + ".intermediate.dense.weight"), g_(prefix + ".intermediate.dense.bias"), I, H, Tf)
         if group_ffn:
@@ -743,11 +768,7 @@ class Engine:
             dqkv[:T, :H].zero_()
         # (packed layout: the rows between the last sequence and T are not the attention kernel's to write, and the weight
         # gradient below contracts over all T rows - backward_encoder zeroes them in both dqkv buffers once per step)
-        aargs = (qkv.data_ptr(), qkv.data_ptr() + 2 * H, qkv.data_ptr() + 4 * H, 3 * H, hip.ptr(mask), hip.ptr(cu),
-                 hip.ptr(qoff), sv["ctx"].data_ptr(), H, dctx.data_ptr(), H, sv["lse"].data_ptr(), delta.data_ptr(),
-                 dqkv.data_ptr(), dqkv.data_ptr() + 2 * H, 3 * H, dqkv.data_ptr() + 4 * H, B, NH, seq, 64,
-                 1.0 / math.sqrt(64.0), p_att, self.seed(lidx, 1))
-        hip.call("stonk_attention_bwd", *aargs, st)
+        self._attention_bwd(qkv, mask, cu, qoff, sv["ctx"], dctx, sv["lse"], delta, dqkv, B, NH, seq, p_att, lidx, st)
         # ---- QKV projection
         w_qkv = (dqkv, sv["x"], g_(prefix + ".attention.self.qkv.weight"), g_(prefix + ".attention.self.qkv.bias"), 3 * H, H, T)
         if group_attn:
