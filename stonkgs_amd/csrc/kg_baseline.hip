@@ -38,7 +38,7 @@
 //   With batch <= 8 the rows read in (B) stay in registers for (D); larger batches re-read them (they are in L2).
 //   The order entries and labels of the next two steps are requested a step ahead, so that their latency is not paid in
 //   line.
-//   DROPOUT. stepkey = H( H(mix(seed) + run) ^ (global step * 0x9E3779B1) ) (n2v_key of n2v_common.h over stonk_seed_mix),
+//   DROPOUT. stepkey = H( H(mix(seed) + run) ^ (global step * 0x9E3779B1) ) (n2v_key of graph_common.h over stonk_seed_mix),
 //   keep(i, d) = stonk_keep(row = i, col = d, stepkey, thr32) of common.h: a pure function of (seed, run, global step, row
 //   in batch, feature). Kept values are multiplied by 1 / (1 - p).
 //   BIAS CORRECTIONS. beta^t by repeated squaring in fp64 - a function of t alone, so cutting a span elsewhere changes no
@@ -49,7 +49,7 @@
 // probabilities; the LOWEST index wins a tie, as torch.argmax does on a first maximum.
 #include <math.h>
 
-#include "n2v_common.h"
+#include "graph_common.h"
 
 // Longest span of steps one launch may walk, chosen so that the longest launch (D 1024, C 16, batch 64) stays below
 // 100 ms on a shared machine. profiles/kg_baseline.md holds the measured time per step at that shape and the arithmetic.
@@ -150,6 +150,7 @@ struct KgbTrain {
 // the lower half of the values still held and hand the upper half to their partner, and the other way round, so the number
 // of shuffles halves with every stage (CM - 1 in all, then log2(64 / CM) on the one value left, instead of 6 CM; the caller takes eight classes at a time at most). Returns
 // the total of class `lane / (64 / CM)`, the same in the 64 / CM lanes of that group. A fixed order of additions.
+// (rank_reduce32 of transe.hip is the same algorithm in fp32 over 32 values.)
 template <int CM>
 __device__ __forceinline__ double kgb_reduce_classes(double (&v)[CM], int lane) {
   int o = 32;
@@ -487,12 +488,10 @@ __global__ __launch_bounds__(256) void kgb_predict_kernel(const float* __restric
 extern "C" int stonk_walk_maxpool(const int32_t* ids, int64_t ld_ids, int64_t n, int L, const float* table, int64_t ld_table,
                                   int64_t N, int D, float* pooled, int64_t ld_pooled, int32_t* errors, void* stream) {
   STONK_CHECK_ARG(ids && table && pooled && errors, STONK_EINVAL);
-  STONK_CHECK_ARG(D >= 64 && D % 64 == 0 && D <= 1024 && L >= 1 && ld_ids >= L && ld_table >= D && ld_pooled >= D &&
-                      N >= 1 && N <= 0x7fffffffLL && n >= 0 && n <= 0x7fffffffLL && ld_table <= 0x7fffffffLL &&
-                      ld_ids <= 0x7fffffffLL && ld_pooled <= 0x7fffffffLL,
+  STONK_CHECK_ARG(graph_dim_ok(D) && L >= 1 && ld_ids >= L && ld_table >= D && ld_pooled >= D && N >= 1 && n >= 0 &&
+                      fits_i32(N, n, ld_table, ld_ids, ld_pooled),
                   STONK_ESHAPE);   // (row offsets are 64-bit products of two values below 2^31)
-  STONK_CHECK_ARG((uintptr_t)ids % 4 == 0 && (uintptr_t)errors % 4 == 0 && (uintptr_t)table % 16 == 0 &&
-                      (uintptr_t)pooled % 16 == 0 && ld_table % 4 == 0 && ld_pooled % 4 == 0,
+  STONK_CHECK_ARG(aligned_to(4, ids, errors) && aligned_to(16, table, pooled) && ld_table % 4 == 0 && ld_pooled % 4 == 0,
                   STONK_EALIGN);
   if (n == 0) return STONK_OK;
   const dim3 grid((unsigned)((n + 3) / 4)), block(256);
@@ -521,16 +520,12 @@ extern "C" int stonk_kgb_train_steps(const float* pooled, int64_t ld_pooled, int
   STONK_CHECK_ARG(p >= 0.f && p < 1.f && lr >= 0. && beta1 >= 0. && beta1 < 1. && beta2 >= 0. && beta2 < 1. && eps >= 0. &&
                       weight_decay >= 0.,
                   STONK_EINVAL);
-  STONK_CHECK_ARG(C >= 2 && C <= STONK_KGB_MAX_CLASSES && batch >= 1 && batch <= STONK_KGB_MAX_BATCH && D >= 64 &&
-                      D % 64 == 0 && D <= 1024 && R >= 0 && R <= 65535 && n >= 1 && n <= 0x7fffffffLL && ld_pooled >= D &&
-                      ld_pooled <= 0x7fffffffLL && n_steps_max >= 0 && n_steps_max <= STONK_KGB_MAX_STEPS &&
+  STONK_CHECK_ARG(C >= 2 && C <= STONK_KGB_MAX_CLASSES && batch >= 1 && batch <= STONK_KGB_MAX_BATCH &&
+                      graph_dim_ok(D) && R >= 0 && R <= 65535 && n >= 1 && ld_pooled >= D && fits_i32(n, ld_pooled) &&
+                      n_steps_max >= 0 && n_steps_max <= STONK_KGB_MAX_STEPS &&
                       ld_order >= (int64_t)n_steps_max * batch && ld_loss >= n_steps_max,
                   STONK_ESHAPE);
-  STONK_CHECK_ARG((uintptr_t)pooled % 4 == 0 && (uintptr_t)labels % 4 == 0 && (uintptr_t)order % 4 == 0 &&
-                      (uintptr_t)n_steps % 4 == 0 && (uintptr_t)first_step % 4 == 0 && (uintptr_t)class_weights % 4 == 0 &&
-                      (uintptr_t)W % 4 == 0 && (uintptr_t)b % 4 == 0 && (uintptr_t)mW % 4 == 0 && (uintptr_t)vW % 4 == 0 &&
-                      (uintptr_t)mb % 4 == 0 && (uintptr_t)vb % 4 == 0 && (uintptr_t)loss % 4 == 0 &&
-                      (uintptr_t)errors % 4 == 0,
+  STONK_CHECK_ARG(aligned_to(4, pooled, labels, order, n_steps, first_step, class_weights, W, b, mW, vW, mb, vb, loss, errors),
                   STONK_EALIGN);
   if (R == 0 || n_steps_max == 0) return STONK_OK;
   KgbTrain a;
@@ -555,12 +550,10 @@ extern "C" int stonk_kgb_predict(const float* pooled, int64_t ld_pooled, int64_t
                                  const float* W, const float* b, int C, float* probs, int32_t* pred, int32_t* errors,
                                  void* stream) {
   STONK_CHECK_ARG(pooled && idx && W && b && probs && pred && errors, STONK_EINVAL);
-  STONK_CHECK_ARG(C >= 2 && C <= STONK_KGB_MAX_CLASSES && D >= 64 && D % 64 == 0 && D <= 1024 && n >= 1 &&
-                      n <= 0x7fffffffLL && ld_pooled >= D && ld_pooled <= 0x7fffffffLL && k >= 0 && k <= 0x7fffffffLL,
+  STONK_CHECK_ARG(C >= 2 && C <= STONK_KGB_MAX_CLASSES && graph_dim_ok(D) && n >= 1 && ld_pooled >= D && k >= 0 &&
+                      fits_i32(n, ld_pooled, k),
                   STONK_ESHAPE);
-  STONK_CHECK_ARG((uintptr_t)pooled % 4 == 0 && (uintptr_t)idx % 4 == 0 && (uintptr_t)W % 4 == 0 && (uintptr_t)b % 4 == 0 &&
-                      (uintptr_t)probs % 4 == 0 && (uintptr_t)pred % 4 == 0 && (uintptr_t)errors % 4 == 0,
-                  STONK_EALIGN);
+  STONK_CHECK_ARG(aligned_to(4, pooled, idx, W, b, probs, pred, errors), STONK_EALIGN);
   if (k == 0) return STONK_OK;
   hipLaunchKernelGGL(kgb_predict_kernel, dim3((unsigned)((k + 3) / 4)), dim3(256), 0, (hipStream_t)stream, pooled,
                      (long)ld_pooled, (long)n, D, idx, (long)k, W, b, C, probs, pred, errors);

@@ -3,9 +3,8 @@
 // stellargraph's EdgeSplitter (negatives) and from scikit-learn's LogisticRegression over a materialised [n, D] feature
 // matrix; stonkgs_amd/link_prediction.py is the host side (edge sampling, the split, L-BFGS, the AUC).
 //
-// RANDOMNESS: the scheme of node2vec.hip (its header states it), SALT = 0x6E326E65:
-//     seedkey = H(seed ^ SALT),  key(i) = H( H(seedkey + i) ^ 0 ),  draw(i, a, c) = H( key(i) + (2 a + c + 1) * 0x85EBCA77 ),
-// mulhi(r, n) = (r * n) >> 32.
+// RANDOMNESS: draw(w, t, a, c) of graph_common.h, salt GRAPH_SALT_NONEDGE: w = i the sample, t = 0, a the attempt, c = 0
+// for u and 1 for v.
 //
 // NEGATIVES (stonk_sample_non_edges). Sample i, attempts a = 0 .. 63: u = mulhi(draw(i,a,0), N), v = mulhi(draw(i,a,1), N);
 // the first attempt with u != v and v not in adj(u) (binary search in u's sorted list; the CSR is symmetric, so one
@@ -27,7 +26,7 @@
 // An example with a node id outside [0, N) adds nothing and gets the score NaN (row 0 is read in its place and discarded).
 #include <math.h>
 
-#include "n2v_common.h"
+#include "graph_common.h"
 
 #define STONK_NONEDGE_ATTEMPTS 64
 // workgroups = rows of `partials`: four per CU on 256 CUs. NOT tuned: up to D 640 all 16 wavefronts of a CU are resident
@@ -48,12 +47,7 @@ __global__ __launch_bounds__(256) void non_edge_kernel(const long* __restrict__ 
     const int cu = (int)n2v_mulhi(n2v_draw(key, a, 0), (uint32_t)N);
     const int cv = (int)n2v_mulhi(n2v_draw(key, a, 1), (uint32_t)N);
     if (cu == cv) continue;
-    const long end = rowptr[cu + 1];
-    long l = rowptr[cu], h = end;   // lower bound of cv in cu's sorted list
-    while (l < h) {
-      const long m = (l + h) >> 1;
-      if (col[m] < cv) l = m + 1; else h = m;
-    }
+    const long end = rowptr[cu + 1], l = csr_lower_bound(col, rowptr[cu], end, cv);
     if (l < end && col[l] == cv) continue;
     u = cu;
     v = cv;
@@ -214,15 +208,13 @@ void launch_linkpred(hipStream_t stream, const float* emb, long ld, int N, const
 extern "C" int stonk_sample_non_edges(const int64_t* rowptr, const int32_t* col, int64_t N, int64_t sample_lo,
                                       int64_t sample_hi, uint32_t seed, int32_t* out, int32_t* failures, void* stream) {
   STONK_CHECK_ARG(rowptr && col && out && failures, STONK_EINVAL);
-  STONK_CHECK_ARG(N >= 1 && N <= 0x7fffffffLL && sample_lo >= 0 && sample_hi >= sample_lo && sample_hi <= 0x3fffffffLL,
+  STONK_CHECK_ARG(N >= 1 && fits_i32(N) && sample_lo >= 0 && sample_hi >= sample_lo && sample_hi <= 0x3fffffffLL,
                   STONK_ESHAPE);   // (2 i + 1 stays an int32-sized element index; i is hashed as 32 bits)
-  STONK_CHECK_ARG((uintptr_t)rowptr % 8 == 0 && (uintptr_t)col % 4 == 0 && (uintptr_t)out % 4 == 0 &&
-                      (uintptr_t)failures % 4 == 0,
-                  STONK_EALIGN);
+  STONK_CHECK_ARG(aligned_to(8, rowptr) && aligned_to(4, col, out, failures), STONK_EALIGN);
   if (sample_hi == sample_lo) return STONK_OK;
   const int64_t blocks = (sample_hi - sample_lo + 255) / 256;
   hipLaunchKernelGGL(non_edge_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const long*)rowptr, col,
-                     (int)N, (long)sample_lo, (long)sample_hi, stonk_hash32(seed ^ 0x6E326E65u), out, failures);
+                     (int)N, (long)sample_lo, (long)sample_hi, stonk_hash32(seed ^ GRAPH_SALT_NONEDGE), out, failures);
   return stonk_launch_status();
 }
 
@@ -231,13 +223,10 @@ extern "C" int64_t stonk_linkpred_partial_rows(void) { return STONK_LINKPRED_ROW
 extern "C" int stonk_linkpred_lossgrad(const float* emb, int64_t ld, int64_t N, int D, const int32_t* pairs, const float* y,
                                        int64_t n, const float* w, float b, float* scores, float* partials, void* stream) {
   STONK_CHECK_ARG(emb && pairs && w && (scores || partials) && (!partials || y), STONK_EINVAL);
-  STONK_CHECK_ARG(D >= 64 && D % 64 == 0 && D <= 1024 && ld >= D && N >= 1 && N <= 0x7fffffffLL && n >= 0 &&
-                      n <= 0x3fffffffffffLL,
+  STONK_CHECK_ARG(graph_dim_ok(D) && ld >= D && N >= 1 && fits_i32(N) && n >= 0 && n <= 0x3fffffffffffLL,
                   STONK_ESHAPE);   // (row offsets are 64-bit: id < 2^31 times ld; N * ld needs no bound of its own)
-  STONK_CHECK_ARG(ld <= 0x7fffffffLL, STONK_ESHAPE);
-  STONK_CHECK_ARG((uintptr_t)emb % 4 == 0 && (uintptr_t)pairs % 8 == 0 && (uintptr_t)y % 4 == 0 && (uintptr_t)w % 4 == 0 &&
-                      (uintptr_t)scores % 4 == 0 && (uintptr_t)partials % 4 == 0,
-                  STONK_EALIGN);
+  STONK_CHECK_ARG(fits_i32(ld), STONK_ESHAPE);
+  STONK_CHECK_ARG(aligned_to(8, pairs) && aligned_to(4, emb, y, w, scores, partials), STONK_EALIGN);
   if (n == 0) return STONK_OK;
   hipStream_t s = (hipStream_t)stream;
 #define STONK_LP_CASE(NF)                                                                                       \

@@ -2,13 +2,8 @@
 // (SGNS) pass over those walks. Replaces what ref:src/stonkgs/models/node2vec.py::run_node2vec gets from `nodevectors`
 // (numba walks on CPU threads) and `gensim` (word2vec "hogwild" threads); stonkgs_amd/node2vec.py is the host side.
 //
-// RANDOMNESS. Every draw is a pure function of (seed, walk w, step / position t, attempt a, which c) - no state, so the
-// result does not depend on launch geometry or on how [0, W) is cut into ranges. With H = stonk_hash32 (common.h) and
-// 32-bit wrap-around arithmetic:
-//     seedkey       = H(seed ^ SALT)                          SALT = 0x6E327677 (walks), 0x6E327367 (SGNS)
-//     key(w, t)     = H( H(seedkey + w) ^ (t * 0x9E3779B1) )
-//     draw(w,t,a,c) = H( key(w, t) + (2 a + c + 1) * 0x85EBCA77 )
-// and mulhi(r, n) = (r * n) >> 32 (64-bit product) maps a draw onto [0, n).
+// RANDOMNESS: draw(w, t, a, c) of graph_common.h, salts GRAPH_SALT_WALKS and GRAPH_SALT_SGNS: w the walk, t the step
+// (walks) or position (SGNS), a the attempt (walks) or the negative's number + 1 (SGNS), c which of an attempt's two draws.
 //
 // WALKS (stonk_random_walks). walk[w][0] = starts ? starts[w] : w % N. Step t >= 1 from cur = walk[w][t-1]
 // (prev = walk[w][t-2]), deg = rowptr[cur+1] - rowptr[cur]:
@@ -31,15 +26,15 @@
 //     rows as read BEFORE the group adds anything; then W_in[ctx_u] += sum_j g(u,j) W_out[tgt_j] (one add per context
 //     occurrence) and W_out[tgt_j] += sum_u g(u,j) W_in[ctx_u] (one add per target occurrence: the sum over the group's
 //     contexts is formed in registers). Repeated nodes - a walk a-b-a, two equal negatives - each contribute their add.
-//   * a lane holds elements {i * 64 + lane} of a row (D / 64 floats), so every load and every atomic wave-instruction covers
-//     256 contiguous bytes; dot products go through wave_sum. The context rows wait in LDS (each lane reads back only what it
-//     wrote: no barrier), the target rows are read again for the context sums - BEFORE any add into W_out is issued.
+//   * rows are held as graph_common.h lays them out; dot products go through wave_sum. The context rows wait in LDS (each
+//     lane reads back only what it wrote: no barrier), the target rows are read again for the context sums - BEFORE any
+//     add into W_out is issued.
 //   * every update is a device-scope float atomic add (global_atomic_add_f32, executed at the memory side: no add is lost
 //     with adders on all eight XCDs). Rows are read with PLAIN loads: per-XCD L2s are not coherent, so an L1-bypassing
 //     (sc1) load could not promise a fresh row either; staleness ends at the launch boundary, which is why the host cuts an
 //     epoch into many launches (node2vec). Plain loads keep the second read of a target row an L1 hit.
 //   * a node id outside [0, N) in `walks` (the -1 rows above) is skipped: as centre the group, as context the pair.
-#include "n2v_common.h"
+#include "graph_common.h"
 
 #define STONK_WALK_ATTEMPTS 32
 #define STONK_WALK_CHUNK 32
@@ -78,11 +73,7 @@ __global__ __launch_bounds__(64) void random_walk_kernel(const long* __restrict_
               next = col[lo + n2v_mulhi(n2v_draw(key, a, 0), deg)];
               uint32_t thr = thr_ret;
               if (next != prev) {
-                long l = plo, h = phi;   // lower bound of `next` in prev's sorted list
-                while (l < h) {
-                  const long m = (l + h) >> 1;
-                  if (col[m] < next) l = m + 1; else h = m;
-                }
+                const long l = csr_lower_bound(col, plo, phi, next);
                 thr = (l < phi && col[l] == next) ? thr_com : thr_oth;
               }
               if ((n2v_draw(key, a, 1) >> 8) < thr) break;
@@ -203,10 +194,7 @@ __global__ __launch_bounds__(64) void sgns_kernel(const int* __restrict__ walks,
         if (i < nf) atomicAdd(dst + i * 64, acc[i]);
     }
   }
-  if (loss_sum_cnt && lane == 0 && loss_cnt > 0.f) {   // one pair of adds per wavefront, not per group
-    atomicAdd(loss_sum_cnt, loss_sum);
-    atomicAdd(loss_sum_cnt + 1, loss_cnt);
-  }
+  wave_loss_flush(loss_sum_cnt, lane, loss_sum, loss_cnt);
 }
 
 }  // namespace
@@ -215,17 +203,15 @@ extern "C" int stonk_random_walks(const int64_t* rowptr, const int32_t* col, int
                                   int64_t walk_lo, int64_t walk_hi, int L, uint32_t thr_return, uint32_t thr_common,
                                   uint32_t thr_other, uint32_t seed, int32_t* walks, int64_t ld, void* stream) {
   STONK_CHECK_ARG(rowptr && col && walks, STONK_EINVAL);
-  STONK_CHECK_ARG(L >= 1 && walk_lo >= 0 && walk_hi >= walk_lo && ld >= L && N >= 1 && N <= 0x7fffffffLL, STONK_ESHAPE);
+  STONK_CHECK_ARG(L >= 1 && walk_lo >= 0 && walk_hi >= walk_lo && ld >= L && N >= 1 && fits_i32(N), STONK_ESHAPE);
   STONK_CHECK_ARG(thr_return <= (1u << 24) && thr_common <= (1u << 24) && thr_other <= (1u << 24), STONK_ESHAPE);
-  STONK_CHECK_ARG((uintptr_t)rowptr % 8 == 0 && (uintptr_t)col % 4 == 0 && (uintptr_t)starts % 4 == 0 &&
-                      (uintptr_t)walks % 4 == 0,
-                  STONK_EALIGN);
+  STONK_CHECK_ARG(aligned_to(8, rowptr) && aligned_to(4, col, starts, walks), STONK_EALIGN);
   if (walk_hi == walk_lo) return STONK_OK;
   const int64_t blocks = (walk_hi - walk_lo + 63) / 64;
-  STONK_CHECK_ARG(blocks <= 0x7fffffffLL, STONK_ESHAPE);
+  STONK_CHECK_ARG(fits_i32(blocks), STONK_ESHAPE);
   hipLaunchKernelGGL(random_walk_kernel, dim3((unsigned)blocks), dim3(64), 0, (hipStream_t)stream, (const long*)rowptr, col,
                      (int)N, starts, (long)walk_lo, (long)walk_hi, L, thr_return, thr_common, thr_other,
-                     stonk_hash32(seed ^ 0x6E327677u), walks, (long)ld);
+                     stonk_hash32(seed ^ GRAPH_SALT_WALKS), walks, (long)ld);
   return stonk_launch_status();
 }
 
@@ -234,21 +220,18 @@ extern "C" int stonk_sgns_step(const int32_t* walks, int64_t ld, int L, int64_t 
                                const uint32_t* alias_thr, const int32_t* alias_idx, float lr, uint32_t seed,
                                float* loss_sum_cnt, void* stream) {
   STONK_CHECK_ARG(walks && W_in && W_out && (negatives <= 0 || (alias_thr && alias_idx)), STONK_EINVAL);
-  STONK_CHECK_ARG(D >= 64 && D % 64 == 0 && D <= 1024 && window >= 1 && negatives >= 0 && L >= 1 && ld >= L && N >= 1 &&
-                      N <= 0x7fffffffLL,
+  STONK_CHECK_ARG(graph_dim_ok(D) && window >= 1 && negatives >= 0 && L >= 1 && ld >= L && N >= 1 && fits_i32(N),
                   STONK_ESHAPE);
   STONK_CHECK_ARG(walk_lo >= 0 && walk_hi >= walk_lo && pos_lo >= 0 && pos_hi >= pos_lo && pos_hi <= L, STONK_ESHAPE);
   STONK_CHECK_ARG((long)window <= 4096 && (long)negatives <= 4096 && sgns_lds_bytes(D, window, negatives) <= 65536,
                   STONK_ESHAPE);   // a group's context rows wait in LDS
-  STONK_CHECK_ARG((uintptr_t)W_in % 16 == 0 && (uintptr_t)W_out % 16 == 0 && (uintptr_t)walks % 4 == 0 &&
-                      (uintptr_t)alias_thr % 4 == 0 && (uintptr_t)alias_idx % 4 == 0 && (uintptr_t)loss_sum_cnt % 4 == 0,
-                  STONK_EALIGN);
+  STONK_CHECK_ARG(aligned_to(16, W_in, W_out) && aligned_to(4, walks, alias_thr, alias_idx, loss_sum_cnt), STONK_EALIGN);
   if (walk_hi == walk_lo || pos_hi == pos_lo) return STONK_OK;
   const int npos = pos_hi - pos_lo;
   const int64_t ngroups = (walk_hi - walk_lo) * npos;
   const int64_t blocks = ngroups < 4096 ? ngroups : 4096;   // wavefronts stride over the groups: 16 per CU
   hipLaunchKernelGGL(sgns_kernel, dim3((unsigned)blocks), dim3(64), (size_t)sgns_lds_bytes(D, window, negatives),
                      (hipStream_t)stream, walks, (long)ld, L, (long)walk_lo, pos_lo, npos, (long)ngroups, W_in, W_out, (int)N,
-                     D, window, negatives, alias_thr, alias_idx, lr, stonk_hash32(seed ^ 0x6E327367u), loss_sum_cnt);
+                     D, window, negatives, alias_thr, alias_idx, lr, stonk_hash32(seed ^ GRAPH_SALT_SGNS), loss_sum_cnt);
   return stonk_launch_status();
 }

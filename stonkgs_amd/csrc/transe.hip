@@ -3,16 +3,11 @@
 // ref:src/stonkgs/constants.py:70 names transe_embeddings_best_model.tsv (the reference's authors made theirs with PyKEEN,
 // outside the package); stonkgs_amd/transe.py is the host side, tests/test_transe_cpu.py restates (a) and (c) in numpy.
 //
-// Tables: ent fp32 [N_e, D], rel fp32 [N_r, D], contiguous; D % 64 == 0, 64 <= D <= 1024. A lane holds elements
-// {i * 64 + lane} of a row (D / 64 floats), so every load and every atomic wave-instruction covers 256 contiguous bytes;
-// dot products and norms go through wave_sum.
+// Tables: ent fp32 [N_e, D], rel fp32 [N_r, D], contiguous; D % 64 == 0, 64 <= D <= 1024 (graph_dim_ok). Rows are held
+// as graph_common.h lays them out; norms go through wave_sum.
 //
-// RANDOMNESS (n2v_common.h; H = stonk_hash32, 32-bit wrap-around arithmetic):
-//     seedkey    = H(seed ^ SALT)                               SALT = 0x74724573
-//     key(g, ep) = H( H(seedkey + g) ^ (ep * 0x9E3779B1) )      g: the GROUP index (not the triple it names), ep: epoch
-//     draw(j, c) = H( key(g, ep) + (2 j + c + 1) * 0x85EBCA77 )
-// and mulhi(r, n) = (r * n) >> 32 (64-bit product). Every draw is a pure function of (seed, g, epoch, j, c): the result
-// does not depend on the grid or on how [0, n) is cut into calls.
+// RANDOMNESS: draw(w, t, a, c) of graph_common.h, salt GRAPH_SALT_TRANSE: w = g, the GROUP index (not the triple it
+// names), t the epoch, a = j the negative; written draw(j, c) below.
 //
 // (a) STEP (stonk_transe_step). One wavefront per group g in [g_lo, g_hi); its triple (h, r, t) = triples[order ? order[g]
 // : g]. An order entry outside [0, n), or an id outside its table, skips the group. Negative j in [0, K):
@@ -51,9 +46,8 @@
 //   distance, and a sum that does not depend on the slot a candidate sits in, so bit-equal rows give bit-equal distances
 //   and equal >= 1 whenever the true entity is a candidate. Few query tiles: the candidate range is split over blockIdx.y
 //   and the counts meet by integer atomics.
-#include "n2v_common.h"
+#include "graph_common.h"
 
-#define TRANSE_SALT 0x74724573u
 #define RANK_QT 16
 #define RANK_WAVES 4
 
@@ -160,10 +154,7 @@ __global__ __launch_bounds__(64) void transe_step_kernel(float* ent, float* rel,
       for (int i = 0; i < nf; ++i) atomicAdd(dst + i * 64, src[i * 64]);
     }
   }
-  if (loss_sum_cnt && lane == 0 && loss_cnt > 0.f) {   // one pair of adds per wavefront, not per group
-    atomicAdd(loss_sum_cnt, loss_sum);
-    atomicAdd(loss_sum_cnt + 1, loss_cnt);
-  }
+  wave_loss_flush(loss_sum_cnt, lane, loss_sum, loss_cnt);
 }
 
 __global__ __launch_bounds__(64) void rows_l2_normalize_kernel(float* table, long ld, long row_lo, long row_hi, int D) {
@@ -185,7 +176,8 @@ __global__ __launch_bounds__(64) void rows_l2_normalize_kernel(float* table, lon
 // one half of its values and hands the other half to its partner, so 16 + 8 + 4 + 2 + 1 + 1 = 32 shuffles do what 32
 // separate butterflies would do in 192. Lane L ends with the full sum of value L >> 1. The additions a value goes through
 // are those of wave_sum - pairs (l, l ^ 32), then (l, l ^ 16), ... - whichever slot it sat in: the result does not depend
-// on the slot, bit for bit.
+// on the slot, bit for bit. (kgb_reduce_classes of kg_baseline.hip is the same algorithm in fp64 over CM values; one template
+// for both changed kgb_train_kernel's code: profiles/refactor_graph_sources.md, section 2.)
 __device__ __forceinline__ float rank_reduce32(float (&a)[2 * RANK_QT], int lane) {
 #pragma unroll
   for (int st = 0; st < 5; ++st) {
@@ -355,8 +347,6 @@ __global__ __launch_bounds__(64 * RANK_WAVES) void transe_rank_kernel(const floa
   }
 }
 
-bool transe_dim_ok(int D) { return D >= 64 && D % 64 == 0 && D <= 1024; }
-
 }  // namespace
 
 extern "C" int stonk_transe_step(float* ent, float* rel, int64_t N_e, int64_t N_r, int D, const int32_t* triples, int64_t n,
@@ -364,31 +354,26 @@ extern "C" int stonk_transe_step(float* ent, float* rel, int64_t N_e, int64_t N_
                                  float lr, uint32_t seed, uint32_t epoch, float* loss_sum_cnt, void* stream) {
   STONK_CHECK_ARG(ent && rel && triples, STONK_EINVAL);
   STONK_CHECK_ARG(norm == 1 || norm == 2, STONK_EINVAL);
-  STONK_CHECK_ARG(transe_dim_ok(D) && negatives >= 1 && N_e >= 1 && N_r >= 1 && N_e <= 0x7fffffffLL && N_r <= 0x7fffffffLL &&
-                      n >= 0 && n <= 0x7fffffffLL,
+  STONK_CHECK_ARG(graph_dim_ok(D) && negatives >= 1 && N_e >= 1 && N_r >= 1 && n >= 0 && fits_i32(N_e, N_r, n),
                   STONK_ESHAPE);
   STONK_CHECK_ARG(g_lo >= 0 && g_hi >= g_lo && g_hi <= n, STONK_ESHAPE);
   STONK_CHECK_ARG((long)negatives * (D + 1) * 4 <= 65536, STONK_ESHAPE);   // a group's G(x_j) wait in LDS
-  STONK_CHECK_ARG((uintptr_t)ent % 16 == 0 && (uintptr_t)rel % 16 == 0 && (uintptr_t)triples % 4 == 0 &&
-                      (uintptr_t)order % 4 == 0 && (uintptr_t)loss_sum_cnt % 4 == 0,
-                  STONK_EALIGN);
+  STONK_CHECK_ARG(aligned_to(16, ent, rel) && aligned_to(4, triples, order, loss_sum_cnt), STONK_EALIGN);
   if (g_hi == g_lo) return STONK_OK;
   const int64_t ngroups = g_hi - g_lo;
   const int64_t blocks = ngroups < 4096 ? ngroups : 4096;   // wavefronts stride over the groups: 16 per CU
   const size_t lds = (size_t)negatives * (D + 1) * 4;
   auto kern = norm == 1 ? transe_step_kernel<1> : transe_step_kernel<2>;
   hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64), lds, (hipStream_t)stream, ent, rel, (int)N_e, (int)N_r, D, triples,
-                     (long)n, order, (long)g_lo, (long)g_hi, negatives, margin, lr, stonk_hash32(seed ^ TRANSE_SALT), epoch,
+                     (long)n, order, (long)g_lo, (long)g_hi, negatives, margin, lr, stonk_hash32(seed ^ GRAPH_SALT_TRANSE), epoch,
                      loss_sum_cnt);
   return stonk_launch_status();
 }
 
 extern "C" int stonk_rows_l2_normalize(float* table, int64_t ld, int64_t row_lo, int64_t row_hi, int D, void* stream) {
   STONK_CHECK_ARG(table, STONK_EINVAL);
-  STONK_CHECK_ARG(transe_dim_ok(D) && ld >= D && ld <= 0x7fffffffLL && row_lo >= 0 && row_hi >= row_lo &&
-                      row_hi <= 0x7fffffffLL,
-                  STONK_ESHAPE);
-  STONK_CHECK_ARG((uintptr_t)table % 16 == 0, STONK_EALIGN);
+  STONK_CHECK_ARG(graph_dim_ok(D) && ld >= D && row_lo >= 0 && row_hi >= row_lo && fits_i32(ld, row_hi), STONK_ESHAPE);
+  STONK_CHECK_ARG(aligned_to(16, table), STONK_EALIGN);
   if (row_hi == row_lo) return STONK_OK;
   const int64_t rows = row_hi - row_lo;
   const int64_t blocks = rows < 8192 ? rows : 8192;
@@ -402,12 +387,8 @@ extern "C" int stonk_transe_rank(const float* ent, const float* rel, int64_t N_e
                                  int64_t n_cand, int32_t* less, int32_t* equal, void* stream) {
   STONK_CHECK_ARG(ent && rel && queries && less && equal && (!cand_ptr || cand || n_cand == 0), STONK_EINVAL);
   STONK_CHECK_ARG((norm == 1 || norm == 2) && (side == 0 || side == 1), STONK_EINVAL);
-  STONK_CHECK_ARG(transe_dim_ok(D) && N_e >= 1 && N_r >= 1 && N_e <= 0x7fffffffLL && N_r <= 0x7fffffffLL && Q >= 0 &&
-                      Q <= 0x7fffffffLL && n_cand >= 0,
-                  STONK_ESHAPE);
-  STONK_CHECK_ARG((uintptr_t)ent % 16 == 0 && (uintptr_t)rel % 16 == 0 && (uintptr_t)queries % 4 == 0 &&
-                      (uintptr_t)cand_ptr % 8 == 0 && (uintptr_t)cand % 4 == 0 && (uintptr_t)less % 4 == 0 &&
-                      (uintptr_t)equal % 4 == 0,
+  STONK_CHECK_ARG(graph_dim_ok(D) && N_e >= 1 && N_r >= 1 && Q >= 0 && fits_i32(N_e, N_r, Q) && n_cand >= 0, STONK_ESHAPE);
+  STONK_CHECK_ARG(aligned_to(16, ent, rel) && aligned_to(8, cand_ptr) && aligned_to(4, queries, cand, less, equal),
                   STONK_EALIGN);
   if (Q == 0) return STONK_OK;
   const int64_t tiles = (Q + RANK_QT - 1) / RANK_QT;

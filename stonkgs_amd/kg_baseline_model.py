@@ -32,6 +32,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _hip as hip
+from .graph_common import as_tensor, need_gpu, to_device
 from .stonkgs_finetuning import get_train_test_splits, weighted_f1_score
 from .stonkgs_model import prepare_df
 
@@ -56,7 +57,7 @@ def _hash32(x):
 
 def dropout_keep_mask(seed: int, run: int, global_step: int, batch: int, d_in: int, p: float) -> np.ndarray:
     """bool [batch, d_in]: the keep decisions of ``stonk_kgb_train_steps`` for one step, restated in numpy (csrc/common.h:
-    ``stonk_keep``; csrc/n2v_common.h: ``n2v_key``). A pure function of (seed, run, global step, row in batch, feature)."""
+    ``stonk_keep``; csrc/graph_common.h: ``n2v_key``). A pure function of (seed, run, global step, row in batch, feature)."""
     seedkey = _hash32(((seed & _M32) * 0x9E3779B9 + 0x85EBCA6B) & _M32)
     stepkey = _hash32(_hash32((seedkey + run) & _M32) ^ (((global_step & _M32) * 0x9E3779B1) & _M32))
     thr = min(max(float(np.float32(p)) * 4294967296.0, 0.0), 4294967295.0)
@@ -144,20 +145,14 @@ def max_steps() -> int:
 
 
 # ---------------------------------------------------------------------------------------------------- kernels
-def _need_gpu():
-    import torch
-
-    if not torch.cuda.is_available():
-        raise hip.StonkHipError("the KG baseline kernels need an MI355X: there is no CPU fallback")
-    return torch
+NO_GPU = "the KG baseline kernels need an MI355X: there is no CPU fallback"
 
 
 def walk_maxpool(ids, table):
     """``pooled[e] = max_t table[ids[e, t]]`` (fp32 [n, D], device) by ``stonk_walk_maxpool``; id -1 is a row of zeros.
     Raises if an id lies outside [-1, N)."""
-    torch = _need_gpu()
-    ids = (ids if torch.is_tensor(ids) else torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int32))).cuda()
-    table = (table if torch.is_tensor(table) else torch.from_numpy(np.ascontiguousarray(table, dtype=np.float32))).cuda()
+    torch = need_gpu(NO_GPU)
+    ids, table = as_tensor(ids, torch.int32).cuda(), as_tensor(table, torch.float32).cuda()
     if ids.dtype != torch.int32 or ids.dim() != 2 or ids.stride(1) != 1 or table.dtype != torch.float32 or \
             table.dim() != 2 or table.stride(1) != 1:
         raise ValueError("ids: int32 [n, L]; table: fp32 [N, D]; both with contiguous rows")
@@ -173,11 +168,10 @@ def walk_maxpool(ids, table):
 
 def kgb_predict(pooled, idx, weight, bias) -> Tuple[np.ndarray, np.ndarray]:
     """``(probabilities fp32 [k, C], arg-max int32 [k])`` of the examples ``idx`` by ``stonk_kgb_predict`` (eval mode)."""
-    torch = _need_gpu()
+    torch = need_gpu(NO_GPU)
     dev = pooled.device
-    idx = torch.as_tensor(np.ascontiguousarray(idx, dtype=np.int32)).to(dev)
-    weight = torch.as_tensor(weight).to(device=dev, dtype=torch.float32).contiguous()
-    bias = torch.as_tensor(bias).to(device=dev, dtype=torch.float32).contiguous()
+    idx = to_device(idx, torch.int32, dev)
+    weight, bias = to_device(weight, torch.float32, dev), to_device(bias, torch.float32, dev)
     C = weight.shape[0]
     probs = torch.empty(idx.shape[0], C, dtype=torch.float32, device=dev)
     pred = torch.empty(idx.shape[0], dtype=torch.int32, device=dev)
@@ -195,7 +189,7 @@ class KGBTrainer:
 
     def __init__(self, pooled, labels, weights: Sequence, biases: Sequence, class_weights: Sequence, lr: float = 1e-3,
                  dropout: float = DROPOUT, weight_decay: float = WEIGHT_DECAY, seed: int = 42):
-        torch = _need_gpu()
+        torch = need_gpu(NO_GPU)
         self.pooled, dev = pooled, pooled.device
         self.labels = torch.as_tensor(np.ascontiguousarray(labels, dtype=np.int32)).to(dev)
         self.W = torch.stack([torch.as_tensor(w, dtype=torch.float32) for w in weights]).to(dev).contiguous()
@@ -273,7 +267,7 @@ class _WalkDataset:
     @property
     def table_device(self):
         if self._table_dev is None:
-            torch = _need_gpu()
+            torch = need_gpu(NO_GPU)
             self._table_dev = torch.from_numpy(self.table).cuda()
         return self._table_dev
 
@@ -345,7 +339,7 @@ class KGEClassificationModel:
     def forward(self, x):
         """``x`` fp32 [B, L, D] embedding sequences -> class probabilities [B, C] (eval mode: dropout acts in ``fit``
         only). The sequences are pooled by ``stonk_walk_maxpool`` as a table of B * L rows."""
-        torch = _need_gpu()
+        torch = need_gpu(NO_GPU)
         B, L, D = x.shape
         rows = x.to(device="cuda", dtype=torch.float32).reshape(B * L, D).contiguous()
         ids = torch.arange(B * L, dtype=torch.int32, device=rows.device).reshape(B, L)

@@ -20,6 +20,7 @@ from typing import Callable, Optional, Tuple
 import numpy as np
 
 from . import _hip as hip
+from .graph_common import as_tensor, csr_to_device, need_gpu, to_device
 
 
 # ---------------------------------------------------------------------------------------------------- examples
@@ -37,23 +38,13 @@ def sample_positive_edges(rowptr, col, p: float = 0.5, seed: int = 0) -> np.ndar
     return np.stack([u[take], v[take]], axis=1).astype(np.int32)
 
 
-def _csr_to_device(rowptr, col, device=None):
-    import torch
-
-    dev = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
-    rp = torch.from_numpy(np.ascontiguousarray(rowptr, dtype=np.int64)).to(dev)
-    cl = torch.from_numpy(np.ascontiguousarray(col, dtype=np.int32)).to(dev) if len(col) else \
-        torch.zeros(1, dtype=torch.int32, device=dev)
-    return dev, rp, cl
-
-
 def sample_non_edges(rowptr, col, count: int, seed: int, device=None):
     """int32 [count, 2] on the device: ordered pairs (u, v), u != v, not adjacent, uniform over such pairs, drawn by
     ``stonk_sample_non_edges`` (a pure function of (seed, row)). Negatives are drawn WITH replacement: two rows may be equal.
     Raises if a sample found no non-edge in its 64 attempts (a graph that is almost complete), naming how many did."""
     import torch
 
-    dev, rp, cl = _csr_to_device(rowptr, col, device)
+    dev, rp, cl = csr_to_device(rowptr, col, device)
     out = torch.empty(int(count), 2, dtype=torch.int32, device=dev)
     failures = torch.zeros(1, dtype=torch.int32, device=dev)
     hip.call("stonk_sample_non_edges", hip.ptr(rp), hip.ptr(cl), len(rowptr) - 1, 0, int(count), seed & 0xFFFFFFFF,
@@ -171,22 +162,17 @@ def roc_auc(scores, labels) -> float:
 
 # ---------------------------------------------------------------------------------------------------- the classifier
 def _device_examples(emb, pairs, y=None):
-    import torch
-
-    if not torch.cuda.is_available():
-        raise hip.StonkHipError("the link-prediction kernels need an MI355X: there is no CPU fallback")
-    emb = emb if torch.is_tensor(emb) else torch.from_numpy(np.ascontiguousarray(emb, dtype=np.float32))
+    torch = need_gpu("the link-prediction kernels need an MI355X: there is no CPU fallback")
+    emb = as_tensor(emb, torch.float32)
     if not emb.is_cuda:
         emb = emb.cuda()
     if emb.dtype != torch.float32 or emb.dim() != 2 or emb.stride(1) != 1:
         raise ValueError("emb: an fp32 [N, D] table with contiguous rows")
-    pairs = pairs if torch.is_tensor(pairs) else torch.from_numpy(np.ascontiguousarray(pairs, dtype=np.int32))
-    pairs = pairs.to(device=emb.device, dtype=torch.int32).contiguous()
+    pairs = to_device(pairs, torch.int32, emb.device)
     if pairs.dim() != 2 or pairs.shape[1] != 2:
         raise ValueError("pairs: int32 [n, 2]")
     if y is not None:
-        y = y if torch.is_tensor(y) else torch.from_numpy(np.ascontiguousarray(y, dtype=np.float32))
-        y = y.to(device=emb.device, dtype=torch.float32).contiguous()
+        y = to_device(y, torch.float32, emb.device)
         if y.shape != (pairs.shape[0],):
             raise ValueError("y: one label per pair")
     return emb, pairs, y
@@ -269,13 +255,12 @@ def link_prediction_report(model, p: float = 0.5, test_size: float = 0.25, seed:
     if getattr(model, "rowptr", None) is None:
         raise ValueError("link_prediction_report needs a fitted Node2Vec (its graph and its table)")
     emb = model._w_in if vectors is None else vectors
-    emb = emb if torch.is_tensor(emb) else torch.from_numpy(np.ascontiguousarray(emb, dtype=np.float32))
-    emb = emb.to(device="cuda", dtype=torch.float32).contiguous()
+    emb = to_device(emb, torch.float32)
     pairs, labels = examples if examples is not None else link_prediction_examples(model.rowptr, model.col, p, seed)
     train, test = stratified_split(labels, test_size, seed)
     order = np.concatenate([train, test])
-    pairs_dev = torch.from_numpy(np.ascontiguousarray(pairs[order], dtype=np.int32)).to(emb.device)
-    y_dev = torch.from_numpy(np.ascontiguousarray(labels[order], dtype=np.float32)).to(emb.device)
+    pairs_dev = to_device(pairs[order], torch.int32, emb.device)
+    y_dev = to_device(labels[order], torch.float32, emb.device)
     k = len(train)
     clf = HadamardLogisticRegression(**logreg_kwargs).fit(emb, pairs_dev[:k], y_dev[:k])   # views: pointer offsets
     z = clf.decision_function(emb, pairs_dev[k:])

@@ -14,12 +14,12 @@ Command line: ``python -m stonkgs_amd.node2vec --pretraining_path edges.tsv --em
 from __future__ import annotations
 
 import itertools
-import os
 from typing import List, Optional, Tuple
 
 import numpy as np
 
 from . import _hip as hip
+from .graph_common import csr_to_device, cuts, decayed_lr, epoch_means, factorize_names, need_gpu, read_columns
 
 LAUNCHES_PER_EPOCH = 64   # rows read inside a launch may be stale (node2vec): an epoch is at least this many
 
@@ -29,23 +29,19 @@ def build_csr(sources, targets) -> Tuple[list, np.ndarray, np.ndarray]:
     or ints. Returns ``(names, rowptr int64 [N+1], col int32 [nnz])``: node i is ``names[i]``, numbered by first appearance
     in the edge list (source before target); both directions of every edge are present, duplicates merged, every
     adjacency list sorted ascending."""
-    import pandas as pd
-
     src, tgt = list(sources), list(targets)
     if len(src) != len(tgt):
         raise ValueError("sources and targets differ in length")
-    inter = np.empty(2 * len(src), dtype=object)
-    inter[0::2], inter[1::2] = src, tgt
-    codes, uniques = pd.factorize(inter)          # first-appearance order
+    codes, uniques = factorize_names(src, tgt)
     n = len(uniques)
     if n == 0:
         raise ValueError("empty edge list")
-    s, t = codes[0::2].astype(np.int64), codes[1::2].astype(np.int64)
+    s, t = codes[:, 0].astype(np.int64), codes[:, 1].astype(np.int64)
     key = np.unique(np.concatenate([s * n + t, t * n + s]))     # sorted by (row, column), duplicates gone
     rows, col = key // n, (key % n).astype(np.int32)
     rowptr = np.zeros(n + 1, dtype=np.int64)
     np.cumsum(np.bincount(rows, minlength=n), out=rowptr[1:])
-    return list(uniques), rowptr, col
+    return uniques, rowptr, col
 
 
 def alias_table(counts, power: float = 0.75) -> Tuple[np.ndarray, np.ndarray]:
@@ -87,18 +83,6 @@ def walk_thresholds(return_weight: float, neighbor_weight: float, other_weight: 
     return tuple(int(np.floor(w / max(ws) * (1 << 24))) for w in ws)
 
 
-def _read_edges(edges_or_path, sep: str):
-    import pandas as pd
-
-    if isinstance(edges_or_path, (str, os.PathLike)):
-        df = pd.read_csv(edges_or_path, sep=sep, usecols=["source", "target"])
-        return df["source"].tolist(), df["target"].tolist()
-    if hasattr(edges_or_path, "columns"):
-        return edges_or_path["source"].tolist(), edges_or_path["target"].tolist()
-    pairs = list(edges_or_path)
-    return [a for a, _ in pairs], [b for _, b in pairs]
-
-
 class Node2Vec:
     """``nodevectors.Node2Vec`` as ref:node2vec.py:314-334 uses it: ``epochs`` walks of ``walklen`` nodes start at every
     node, one skip-gram pass (``window``, ``negative`` noise words, learning rate ``alpha`` -> ``min_alpha``) runs over them.
@@ -138,11 +122,8 @@ class Node2Vec:
         """int32 [epochs * N, walklen] on the device: row e * N + n is the walk of epoch e that starts at node n."""
         import torch
 
-        dev = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        dev, rp, cl = csr_to_device(rowptr, col, device)
         n = len(rowptr) - 1
-        rp = torch.from_numpy(np.ascontiguousarray(rowptr, dtype=np.int64)).to(dev)
-        cl = torch.from_numpy(np.ascontiguousarray(col, dtype=np.int32)).to(dev) if len(col) else \
-            torch.zeros(1, dtype=torch.int32, device=dev)
         total = self.epochs * n
         walks = torch.empty(total, self.walklen, dtype=torch.int32, device=dev)
         hip.call("stonk_random_walks", hip.ptr(rp), hip.ptr(cl), n, 0, 0, total, self.walklen, *self.thresholds,
@@ -154,8 +135,7 @@ class Node2Vec:
         LAUNCHES_PER_EPOCH ranges of walks - and of positions where there are fewer walks than that."""
         n_w = min(n, LAUNCHES_PER_EPOCH)
         n_p = min(self.walklen, -(-LAUNCHES_PER_EPOCH // n_w))
-        wcuts = [n * i // n_w for i in range(n_w + 1)]
-        pcuts = [self.walklen * i // n_p for i in range(n_p + 1)]
+        wcuts, pcuts = cuts(n, n_w), cuts(self.walklen, n_p)
         return [(e, e * n + wcuts[i], e * n + wcuts[i + 1], pcuts[j], pcuts[j + 1])
                 for e in range(self.epochs) for i in range(n_w) for j in range(n_p)]
 
@@ -182,25 +162,19 @@ class Node2Vec:
         loss = torch.zeros(len(plan), 2, device=dev)
         stream = hip.stream_ptr()
         for i, (_, w_lo, w_hi, p_lo, p_hi) in enumerate(plan):
-            lr = self.alpha - (self.alpha - self.min_alpha) * i / len(plan)
+            lr = decayed_lr(self.alpha, self.min_alpha, i, len(plan))
             hip.call("stonk_sgns_step", hip.ptr(walks), walks.shape[1], walks.shape[1], w_lo, w_hi, p_lo, p_hi,
                      hip.ptr(w_in), hip.ptr(w_out), n, d, self.window, self.negative, hip.ptr(a_thr), hip.ptr(a_idx), lr,
                      self.seed & 0xFFFFFFFF, loss[i].data_ptr(), stream)
-        per = loss.double().cpu().numpy()
-        epoch_of = np.array([e for e, *_ in plan])
-        self.loss_history = [float(per[epoch_of == e, 0].sum() / max(per[epoch_of == e, 1].sum(), 1.0))
-                             for e in range(self.epochs)]
+        self.loss_history = epoch_means(loss, [e for e, *_ in plan], self.epochs)
         self._w_out = w_out
         return w_in
 
     # ------------------------------------------------------------------ the nodevectors surface
     def fit(self, edges_or_path, sep: str = "\t"):
         """``edges_or_path``: a TSV with ``source`` and ``target`` columns, a DataFrame with them, or (source, target) pairs."""
-        import torch
-
-        if not torch.cuda.is_available():
-            raise hip.StonkHipError("Node2Vec.fit needs an MI355X: the walk and skip-gram kernels have no CPU fallback")
-        src, tgt = _read_edges(edges_or_path, sep)
+        need_gpu("Node2Vec.fit needs an MI355X: the walk and skip-gram kernels have no CPU fallback")
+        src, tgt = read_columns(edges_or_path, sep, ("source", "target"))
         self.names, rowptr, col = build_csr(src, tgt)
         self.rowptr, self.col = rowptr, col
         self._index = {name: i for i, name in enumerate(self.names)}
@@ -297,7 +271,7 @@ def run_node2vec_hpo(pretraining_path: str, sep: str = "\t", delete_database: bo
     if seed is None:
         seed = int(np.random.randint(1, 2 ** 31 - 1))
     trials = hpo_trials(search_space or HPO_SEARCH_SPACE, n_trials, seed)
-    src, tgt = _read_edges(pretraining_path, sep)
+    src, tgt = read_columns(pretraining_path, sep, ("source", "target"))
     edges = list(zip(src, tgt))
     _, rowptr, col = build_csr(src, tgt)
     examples = link_prediction_examples(rowptr, col, seed=seed)

@@ -15,12 +15,12 @@ Command line: ``python -m stonkgs_amd.transe --pretraining_path triples.tsv --em
 from __future__ import annotations
 
 import logging
-import os
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
 from . import _hip as hip
+from .graph_common import cuts, decayed_lr, epoch_means, factorize_names, need_gpu, read_columns, to_device
 
 logger = logging.getLogger(__name__)
 
@@ -32,36 +32,20 @@ METRICS = ("mrr", "mean_rank", "hits@1", "hits@3", "hits@10")
 def build_triples(sources, relations, targets) -> Tuple[list, list, np.ndarray]:
     """``(entity_names, relation_names, int32 [n, 3])`` of (head, relation, tail) ids; names numbered by first appearance
     (an entity: source before target of the same triple)."""
-    import pandas as pd
-
     src, rel, tgt = list(sources), list(relations), list(targets)
     if not len(src) == len(rel) == len(tgt):
         raise ValueError("sources, relations and targets differ in length")
     if not src:
         raise ValueError("empty triple list")
-    inter = np.empty(2 * len(src), dtype=object)
-    inter[0::2], inter[1::2] = src, tgt
-    e_codes, e_names = pd.factorize(inter)
-    r_obj = np.empty(len(rel), dtype=object)
-    r_obj[:] = rel
-    r_codes, r_names = pd.factorize(r_obj)
-    triples = np.stack([e_codes[0::2], r_codes, e_codes[1::2]], axis=1).astype(np.int32)
-    return list(e_names), list(r_names), np.ascontiguousarray(triples)
+    e_codes, e_names = factorize_names(src, tgt)
+    r_codes, r_names = factorize_names(rel)
+    triples = np.stack([e_codes[:, 0], r_codes[:, 0], e_codes[:, 1]], axis=1).astype(np.int32)
+    return e_names, r_names, np.ascontiguousarray(triples)
 
 
 def _read_triples(triples_or_path, sep: str):
-    """``(sources, relations, targets)`` of a TSV with ``source``, ``relation`` and ``target`` columns (the reference's
-    pre-training file has them), a DataFrame with them, or (source, relation, target) tuples."""
-    import pandas as pd
-
-    if isinstance(triples_or_path, (str, os.PathLike)):
-        df = pd.read_csv(triples_or_path, sep=sep, usecols=["source", "relation", "target"])
-        return df["source"].tolist(), df["relation"].tolist(), df["target"].tolist()
-    if hasattr(triples_or_path, "columns"):
-        return (triples_or_path["source"].tolist(), triples_or_path["relation"].tolist(),
-                triples_or_path["target"].tolist())
-    rows = list(triples_or_path)
-    return [a for a, _, _ in rows], [b for _, b, _ in rows], [c for _, _, c in rows]
+    """``(sources, relations, targets)`` of a TSV or DataFrame with ``source``, ``relation``, ``target`` columns, or of tuples."""
+    return read_columns(triples_or_path, sep, ("source", "relation", "target"))
 
 
 def known_index(triples) -> Dict[str, Dict[tuple, list]]:
@@ -122,34 +106,21 @@ def evaluation_report(ranks_tail, ranks_head) -> Dict[str, object]:
 
 
 # ---------------------------------------------------------------------------------------------------- kernels
-def _need_gpu():
-    import torch
-
-    if not torch.cuda.is_available():
-        raise hip.StonkHipError("TransE needs an MI355X: the step, normalise and rank kernels have no CPU fallback")
-    return torch
-
-
-def _dev(x, dtype):
-    torch = _need_gpu()
-    if torch.is_tensor(x):
-        return x.to(device="cuda", dtype=dtype).contiguous()
-    np_dtype = {torch.float32: np.float32, torch.int32: np.int32, torch.int64: np.int64}[dtype]
-    return torch.from_numpy(np.ascontiguousarray(x, dtype=np_dtype)).cuda()
+NO_GPU = "TransE needs an MI355X: the step, normalise and rank kernels have no CPU fallback"
 
 
 def transe_rank(ent, rel, queries, side: int, norm: int, cand_ptr=None, cand=None) -> Tuple[np.ndarray, np.ndarray]:
     """``(less, equal)`` int32 [Q] by ``stonk_transe_rank``: the candidates closer than / as close as the true entity.
     ``ent`` / ``rel``: tables (numpy or device tensors); ``queries`` int [Q, 3]; candidates: every entity, or the lists
     ``cand[cand_ptr[q]:cand_ptr[q + 1]]``."""
-    torch = _need_gpu()
-    ent, rel = _dev(ent, torch.float32), _dev(rel, torch.float32)
-    q = _dev(np.asarray(queries).reshape(-1, 3) if not torch.is_tensor(queries) else queries, torch.int32)
+    torch = need_gpu(NO_GPU)
+    ent, rel = to_device(ent, torch.float32), to_device(rel, torch.float32)
+    q = to_device(np.asarray(queries).reshape(-1, 3) if not torch.is_tensor(queries) else queries, torch.int32)
     n_q = q.shape[0]
     less = torch.empty(max(n_q, 1), dtype=torch.int32, device="cuda")
     equal = torch.empty(max(n_q, 1), dtype=torch.int32, device="cuda")
-    ptr = _dev(cand_ptr, torch.int64) if cand_ptr is not None else None
-    lst = _dev(cand, torch.int32) if cand_ptr is not None and len(cand) else None
+    ptr = to_device(cand_ptr, torch.int64) if cand_ptr is not None else None
+    lst = to_device(cand, torch.int32) if cand_ptr is not None and len(cand) else None
     hip.call("stonk_transe_rank", hip.ptr(ent), hip.ptr(rel), ent.shape[0], rel.shape[0], ent.shape[1], norm, hip.ptr(q), n_q,
              side, hip.ptr(ptr), hip.ptr(lst), 0 if lst is None else lst.shape[0], hip.ptr(less), hip.ptr(equal),
              hip.stream_ptr())
@@ -203,14 +174,12 @@ class TransE:
     def launch_plan(self, n: int) -> List[Tuple[int, int, int]]:
         """``(epoch, g_lo, g_hi)`` per launch: every epoch's n groups cut into ``launches_per_epoch`` ranges (n ranges of
         one group where there are fewer groups than that)."""
-        cuts_n = min(n, self.launches_per_epoch)
-        cuts = [n * i // cuts_n for i in range(cuts_n + 1)]
-        return [(e, cuts[i], cuts[i + 1]) for e in range(self.epochs) for i in range(cuts_n)]
+        parts = min(n, self.launches_per_epoch)
+        bounds = cuts(n, parts)
+        return [(e, bounds[i], bounds[i + 1]) for e in range(self.epochs) for i in range(parts)]
 
     def launch_lr(self, i: int, n_launches: int) -> float:
-        if self.min_lr is None:
-            return self.lr
-        return self.lr - (self.lr - self.min_lr) * i / n_launches
+        return decayed_lr(self.lr, self.min_lr, i, n_launches)
 
     def epoch_order(self, n: int, epoch: int) -> np.ndarray:
         """int32 [n]: the seeded permutation of the triples that epoch ``epoch`` walks (group g is triple order[g])."""
@@ -223,9 +192,9 @@ class TransE:
     def train(self, triples, n_entities: int, n_relations: int):
         """All epochs over ``triples`` (int [n, 3]); returns ``(ent, rel)`` (fp32, device). ``loss_history``: the mean loss
         per term and epoch."""
-        torch = _need_gpu()
+        torch = need_gpu(NO_GPU)
         d = self.n_components
-        tri = _dev(np.asarray(triples).reshape(-1, 3), torch.int32)
+        tri = to_device(np.asarray(triples).reshape(-1, 3), torch.int32)
         n = tri.shape[0]
         ent0, rel0 = self.initial_vectors(n_entities, n_relations)
         ent, rel = ent0.cuda(), rel0.cuda()
@@ -241,23 +210,20 @@ class TransE:
                      self.seed & 0xFFFFFFFF, e, loss[i].data_ptr(), stream)
             if self.normalizes_after(i, len(plan)):
                 hip.call("stonk_rows_l2_normalize", hip.ptr(ent), d, 0, n_entities, d, stream)
-        per = loss.double().cpu().numpy()
-        epoch_of = np.array([e for e, _, _ in plan])
-        self.loss_history = [float(per[epoch_of == e, 0].sum() / max(per[epoch_of == e, 1].sum(), 1.0))
-                             for e in range(self.epochs)]
+        self.loss_history = epoch_means(loss, [e for e, _, _ in plan], self.epochs)
         return ent, rel
 
     def fit(self, triples_or_path, sep: str = "\t"):
         """``triples_or_path``: a TSV with ``source``, ``relation`` and ``target`` columns, a DataFrame with them, or
         (source, relation, target) tuples."""
-        _need_gpu()
+        need_gpu(NO_GPU)
         src, rel, tgt = _read_triples(triples_or_path, sep)
         names_e, names_r, triples = build_triples(src, rel, tgt)
         return self.fit_ids(names_e, names_r, triples)
 
     def fit_ids(self, entity_names, relation_names, triples):
         """``fit`` on triples that are ids already (``build_triples``' output, or a training share of it)."""
-        _need_gpu()
+        need_gpu(NO_GPU)
         self.entity_names, self.relation_names = list(entity_names), list(relation_names)
         self.triples = np.ascontiguousarray(np.asarray(triples).reshape(-1, 3), dtype=np.int32)
         self._entity_index = {name: i for i, name in enumerate(self.entity_names)}

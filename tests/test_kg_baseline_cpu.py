@@ -145,7 +145,7 @@ def _h(x):
 
 
 def _keep_scalar(seed, run, step, i, d, p):
-    """csrc/common.h and n2v_common.h, one element at a time in Python integers."""
+    """csrc/common.h and graph_common.h, one element at a time in Python integers."""
     seedkey = _h(seed * 0x9E3779B9 + 0x85EBCA6B)
     stepkey = _h(_h(seedkey + run) ^ ((step * 0x9E3779B1) & 0xFFFFFFFF))
     x = ((i * 0x9E3779B1 + stepkey) & 0xFFFFFFFF) ^ ((d * 0x85EBCA77) & 0xFFFFFFFF)
