@@ -3,9 +3,11 @@
 run on given ``inputs_embeds``.
 
     BigBirdEncoderConfig   the fields of hf BigBirdConfig the encoder reads, and what the kernels are built for
-    BigBirdEngine          engine.Engine with the block-sparse attention core (masked queries as HuggingFace has them),
-                           gelu_new behind the FFN-up GEMM, BigBird's embeddings (dropout BEFORE the LayerNorm), no
-                           attention-probability dropout; the GEMM / LayerNorm chain of a layer is the base class's
+    BigBirdEngine          layer_engine.LayerEngine with the block-sparse attention core (masked queries as HuggingFace has
+                           them) and gelu_new behind the FFN-up GEMM in the place of its four layer methods, plus what this
+                           encoder puts around the layers: BigBird's embeddings (dropout BEFORE the LayerNorm) and the
+                           pooler. No attention-probability dropout; the GEMM / LayerNorm chain of a layer, the workspace,
+                           the streams and the derived weights are the base class's
     BigBirdEncoderModel    FlatBufferModel that loads a BigBirdModel state dict (plain, or under ``bert.``), differentiable:
                            forward(inputs_embeds, attention_mask, token_type_ids) -> (sequence_output, pooler_output)
 
@@ -28,7 +30,7 @@ import torch
 
 from . import _hip as hip
 from .bigbird_attention import BLOCK, BlockSparsePlan, bigbird_rand_attn
-from .engine import F32, Engine, padded_rows
+from .layer_engine import F32, LayerEngine, padded_rows
 from .flat_model import FlatBufferModel, _load_weights_file
 from .params import FlatStore, _linear, build_bert_tree, trainable_specs
 
@@ -166,8 +168,8 @@ def map_state_dict(state_dict: Dict[str, torch.Tensor]) -> Tuple[Dict[str, torch
 
 
 # ------------------------------------------------------------------------------------------------ engine
-class BigBirdEngine(Engine):
-    """The encoder's launches. A layer is `Engine.layer_fwd` / `layer_bwd` in the padded layout with four methods replaced:
+class BigBirdEngine(LayerEngine):
+    """The encoder's launches. A layer is `LayerEngine.layer_fwd` / `layer_bwd` in the padded layout with four methods replaced:
     the attention core (stonk_block_sparse_attention_*_ex with STONK_BSA_ZERO_MASKED_QUERIES, no probability dropout) and
     the FFN activation (bias-only GEMM, then stonk_gelu_new_*: the GEMM epilogues carry the erf form only)."""
 
@@ -175,7 +177,7 @@ class BigBirdEngine(Engine):
     KEY_ERROR_BITS = 0
 
     def __init__(self, cfg: BigBirdEncoderConfig, store: FlatStore, device):
-        super().__init__(cfg, store, None, 0, device)
+        super().__init__(cfg, store, device)
         self.plans: List[BlockSparsePlan] = []   # one per layer, for the sequence length of the call in flight
         self.generation = 0                      # training forwards so far: a backward must belong to the latest
 

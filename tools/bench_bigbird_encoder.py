@@ -18,7 +18,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from stonkgs_amd import _hip as hip  # noqa: E402
 from stonkgs_amd.bigbird_encoder import BigBirdEncoderConfig, BigBirdEncoderModel, BigBirdEngine  # noqa: E402
-from stonkgs_amd.engine import Engine  # noqa: E402
+from stonkgs_amd.layer_engine import LayerEngine  # noqa: E402
 
 LAYERS, S = int(os.environ.get("LAYERS", 12)), int(os.environ.get("S", 4096))
 N, REPS = int(os.environ.get("N", 3)), int(os.environ.get("REPS", 5))
@@ -27,8 +27,8 @@ BATCHES = [int(b) for b in os.environ.get("B", "1,2,4").split(",")]
 
 class DenseAttentionEngine(BigBirdEngine):
     """The comparison arm: the dense attention core (no probability dropout), everything else the encoder's."""
-    _attention_fwd = Engine._attention_fwd
-    _attention_bwd = Engine._attention_bwd
+    _attention_fwd = LayerEngine._attention_fwd
+    _attention_bwd = LayerEngine._attention_bwd
 
 
 def window(fn, n):
